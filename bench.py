@@ -29,6 +29,18 @@ through the C ABI a cgo caller would use (mh_multi_create over devices
 mh_multi_dev_htree_build_entries_fixed per step), instead of N
 torch.distributed ranks.
 
+A plain run sets up, warms up, times --steps steps and prints the result line
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  --full adds
+everything beside the headline figure, after the timed region: the root check
+against the oracle (exit 1 on a mismatch), the per-kernel timing passes and
+the roofline figures, the single-build rate and the CPU baseline.
+
+--dump-outputs DIR writes what the last timed step computed (level array and
+root; the ahtree's digests and roots; the tx log's headers, Alh and statuses)
+as DIR/<name>.npy in float32, large outputs as a fixed, seeded sample of
+their rows.  The inputs are a fixed splitmix64 stream, so two builds of the
+library run with the same arguments can be compared file for file.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -86,7 +98,18 @@ def parse():
                    help="override entries per GPU (--api cabi --config c3: total appends)")
     p.add_argument("--n0", type=int, default=10 ** 6 + 3,
                    help="--api cabi --config c3: size of the tree the batch is appended onto")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run everything beside the headline figure: "
+                        "the root check against the oracle (exit 1 on a mismatch), the "
+                        "per-kernel timing passes and roofline figures, the single-build rate "
+                        "and the CPU baseline.  Off by default: a plain run sets up, warms up, "
+                        "times the steps and prints the result line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step computed as "
+                        "DIR/<name>.npy (float32; outputs above the size cap as a fixed, seeded "
+                        "sample of their rows)")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="with --full: leave the CPU baseline out")
     p.add_argument("--launch-check", action="store_true",
                    help="only bring up the N-rank process group (gloo, no GPU work) and print "
                         "its world size: tests the --gpus N launcher on a CPU host")
@@ -138,6 +161,38 @@ def host_threads(share=1):
     except (AttributeError, OSError):
         avail = os.cpu_count() or 1
     return max(1, avail // max(share, 1))
+
+
+DUMP_BUDGET = 48 << 20  # bytes of float32 one run writes under --dump-outputs, all files
+DUMP_SEED = 20261019
+
+
+def dump_outputs(path, outputs, share=1):
+    """--dump-outputs: write every (rows, width) uint8 output of the last timed
+    step (device tensor or host array) as path/<name>.npy, one float32 per
+    byte.  The byte budget is split evenly over the outputs (and over `share`
+    processes writing to the same directory); an output above its part is cut
+    to a fixed sample of its rows -- the first 256, the last 1024 (the top
+    levels and the root of a level array) and seeded random ones -- the same
+    rows on every run of the same arguments."""
+    os.makedirs(path, exist_ok=True)
+    part = DUMP_BUDGET // max(share, 1) // max(len(outputs), 1)
+    for name, x in outputs.items():
+        rows, width = x.shape
+        cap = max(part // (4 * width), 1)
+        if rows > cap:
+            rng = np.random.default_rng(DUMP_SEED)
+            idx = np.union1d(np.arange(min(256, rows)), np.arange(max(rows - 1024, 0), rows))
+            idx = idx[-cap:] if len(idx) >= cap else \
+                np.union1d(idx, rng.choice(rows, cap - len(idx), replace=False))
+            if isinstance(x, np.ndarray):
+                x = x[idx]
+            else:
+                import torch
+                x = x[torch.from_numpy(idx).to(x.device)]
+        if not isinstance(x, np.ndarray):
+            x = x.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), x.astype(np.float32))
 
 
 def shard_seed(rank, n, val, strong):
@@ -290,6 +345,17 @@ def secondary_config(a):
     file's JSON contract, with the oracle timed beside it (cpu_baseline)."""
     import torch  # noqa: F401
     import bench_workloads as bw
+    if a.dump_outputs:
+        raise SystemExit("--dump-outputs: not with --config c3 / c5 (bench_workloads.py keeps "
+                         "their outputs to itself); --api cabi --config c3 writes the ahtree's")
+
+    def emit(cpu):
+        out.update({"n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
+                    "ms_per_step": r["ms_per_step"], "scaling": "weak", "vs_baseline": None,
+                    "dtype": "u32", "data": "synthetic (splitmix64, generated in HBM)",
+                    "full": a.full, "cpu_baseline": cpu})
+        print(json.dumps(out), flush=True)
+
     wa = bw.make_parser().parse_args(["--workload", a.config, "--steps", str(a.steps),
                                       "--warmup", str(a.warmup)])
     r = bw.run_single(wa)
@@ -313,6 +379,8 @@ def secondary_config(a):
                             "sha": {"gcomp_per_s": r["gcomp_per_s"],
                                     "peak_gcomp_per_s": SHA_PEAK_GCOMPS,
                                     "frac": round(r["gcomp_per_s"] / SHA_PEAK_GCOMPS, 4)}}}
+        if not a.full or a.no_cpu_baseline:
+            return emit(None)
         # CPU: the oracle's batch append over the first 2^20 payloads (same stream)
         n = 1 << 20
         pay = orc.fill_random(32 * n, 3).reshape(n, 32)
@@ -344,6 +412,8 @@ def secondary_config(a):
                                     "peak_gcomp_per_s": SHA_PEAK_GCOMPS,
                                     "frac": round(r["gcomp_per_s"] / SHA_PEAK_GCOMPS, 4)}},
                "proof_generation": r.get("proof_generation")}
+        if not a.full or a.no_cpu_baseline:
+            return emit(None)
         # CPU: the oracle's VerifyInclusion over 2^17 proofs of a 2^24-leaf tree
         # whose levels come from the device build of the same digests
         import immustore_amd as m
@@ -377,11 +447,7 @@ def secondary_config(a):
                "kind": "port", "sample": "oracle VerifyInclusion of 2^17 depth-24 proofs, single "
                                          "thread, SHA-NI=%s, best of 3 = %.3f s" % (
                                              orc.has_shani(), best)}
-    out.update({"n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
-                "ms_per_step": r["ms_per_step"], "scaling": "weak", "vs_baseline": None,
-                "dtype": "u32", "data": "synthetic (splitmix64, generated in HBM)",
-                "cpu_baseline": None if a.no_cpu_baseline else cpu})
-    print(json.dumps(out), flush=True)
+    emit(cpu)
 
 
 def free_port():
@@ -499,8 +565,35 @@ def cabi_main(a):
     t0 = time.perf_counter()
     run_steps(a.steps)
     elapsed = time.perf_counter() - t0
-    # device 0's kernel time from a pass after the timed region (the timing
-    # events stay out of it)
+    if a.dump_outputs:
+        # the last timed build's outputs on every device (clique (steps-1) % D)
+        j = (a.steps - 1) % D
+        o = {}
+        for d in range(K):
+            tag = "_dev%d" % d if K > 1 else ""
+            o["levels" + tag] = lvs[j][d].view(-1, 32)
+            o["top_levels" + tag] = tops[j][d].view(-1, 32)
+            o["root" + tag] = rts[j][d].view(1, 32)
+        dump_outputs(a.dump_outputs, o)
+    out = {
+        "metric": "device-resident GiB/s hashed, htree build, 1M x 1KiB leaves" if a.config == "c2"
+        else "device-resident GiB/s hashed, htree build, 2^23 x 4KiB leaves per GPU (configs[3])",
+        "value": round(K * n * VAL / elapsed * a.steps / 2 ** 30, 3),
+        "unit": "GiB/s", "n_gpus": K, "api": "cabi", "rccl_ranks": K if md.uses_rccl() else 0,
+        "process_group": None, "steps": a.steps, "warmup": a.warmup,
+        "clock_prewarm": {"seconds": a.prewarm, "builds": pre},
+        "ms_per_step": round(elapsed / a.steps * 1e3, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "u32",
+        "data": "synthetic (splitmix64 values generated in HBM, keys BE64(i))",
+        "full": a.full,
+    }
+    if not a.full:
+        print(json.dumps(out), flush=True)
+        for x in mds:
+            x.close()
+        return
+    # ---- --full.  Device 0's kernel time from a pass after the timed region
+    # (the timing events stay out of it)
     N.check(L.mh_ctx_timing_reset(c0))
     N.check(L.mh_ctx_set_timing(c0, 1))
     for _ in range(min(a.steps, 50)):
@@ -539,16 +632,7 @@ def cabi_main(a):
     alg_bytes = n * (VAL + KEY_LEN) + 32 * sum(-(-n // (1 << l)) for l in range(ltop + 1))
     achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
     step_achieved = alg_bytes / (elapsed / a.steps) / 1e9
-    out = {
-        "metric": "device-resident GiB/s hashed, htree build, 1M x 1KiB leaves" if a.config == "c2"
-        else "device-resident GiB/s hashed, htree build, 2^23 x 4KiB leaves per GPU (configs[3])",
-        "value": round(K * n * VAL / elapsed * a.steps / 2 ** 30, 3),
-        "unit": "GiB/s", "n_gpus": K, "api": "cabi", "rccl_ranks": K if md.uses_rccl() else 0,
-        "process_group": None, "steps": a.steps, "warmup": a.warmup,
-        "clock_prewarm": {"seconds": a.prewarm, "builds": pre},
-        "ms_per_step": round(elapsed / a.steps * 1e3, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "u32",
-        "data": "synthetic (splitmix64 values generated in HBM, keys BE64(i))",
+    out.update({
         "config": {"workload": "htree build over %d x %d B entries per device, %d devices, "
                                "one process (mh_multi_dev_htree_build_entries_fixed)" % (n, VAL, K),
                    "entries_per_gpu": n, "value_len": VAL, "key_len": KEY_LEN,
@@ -565,7 +649,7 @@ def cabi_main(a):
                                   "frac": round(step_achieved / HBM_PEAK_GBS, 4)}},
         "cpu_baseline": None,
         "root_check": rcheck,
-    }
+    })
     print(json.dumps(out), flush=True)
     for x in mds:
         x.close()
@@ -696,7 +780,27 @@ def cabi_c3(a):
     md.synchronize()
     elapsed = time.perf_counter() - t0
     ms = elapsed / a.steps * 1e3
-    # device 0's kernels in a pass after the timed region
+    if a.dump_outputs:
+        # every range's new dLog digests and per-append roots
+        o = {}
+        for d in range(G):
+            o["dlog_range%d" % d] = dl[d].view(-1, 32)
+            o["roots_range%d" % d] = ro[d].view(-1, 32)
+        dump_outputs(a.dump_outputs, o)
+    out = {"metric": "ahtree replay append (syncBinaryLinking), %d x %d B payloads onto a tree of "
+                     "%d, through the C ABI across %d device(s)" % (total, plen, n0, K),
+           "value": round(total / elapsed * a.steps / 1e6, 3), "unit": "M appends/s",
+           "n_gpus": K, "api": "cabi", "rccl_ranks": K if (md.uses_rccl() and G > 1) else 0,
+           "steps": a.steps, "warmup": a.warmup,
+           "clock_prewarm": {"seconds": a.prewarm, "appends_batches": pre},
+           "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "strong",
+           "vs_baseline": None, "dtype": "u32",
+           "data": "synthetic (splitmix64 payloads generated in HBM)", "full": a.full}
+    if not a.full:
+        print(json.dumps(out), flush=True)
+        md.close()
+        return
+    # ---- --full.  Device 0's kernels in a pass after the timed region
     N.check(L.mh_ctx_timing_reset(c0))
     N.check(L.mh_ctx_set_timing(c0, 1))
     kp = min(a.steps, 10)
@@ -741,15 +845,7 @@ def cabi_c3(a):
               "corrupted_ranges": corrupted, "seconds": round(time.perf_counter() - tc, 2)}
     new_digests = up(n0 + total) - up(n0)
     alg = total * plen + 32 * new_digests
-    out = {"metric": "ahtree replay append (syncBinaryLinking), %d x %d B payloads onto a tree of "
-                     "%d, through the C ABI across %d device(s)" % (total, plen, n0, K),
-           "value": round(total / elapsed * a.steps / 1e6, 3), "unit": "M appends/s",
-           "n_gpus": K, "api": "cabi", "rccl_ranks": K if (md.uses_rccl() and G > 1) else 0,
-           "steps": a.steps, "warmup": a.warmup,
-           "clock_prewarm": {"seconds": a.prewarm, "appends_batches": pre},
-           "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "strong",
-           "vs_baseline": None, "dtype": "u32",
-           "data": "synthetic (splitmix64 payloads generated in HBM)",
+    out.update({
            "config": {"workload": "mh_multi_dev_ahtree_append_batch onto old peaks from "
                                   "mh_dev_ahtree_peaks", "n0": n0, "appends": total,
                       "payload_len": plen, "ranges": G, "range_bounds": b,
@@ -765,7 +861,7 @@ def cabi_c3(a):
                         "sha": {"gcomp_per_s": round((total + 2 * (new_digests - total)) /
                                                      (ms * 1e-3) / 1e9, 2),
                                 "peak_gcomp_per_s": SHA_PEAK_GCOMPS}},
-           "cpu_baseline": None, "root_check": rcheck}
+           "cpu_baseline": None, "root_check": rcheck})
     print(json.dumps(out), flush=True)
     md.close()
     if not ok:
@@ -828,7 +924,25 @@ def cabi_txlog(a):
         step()
     elapsed = time.perf_counter() - t0
     ms = elapsed / a.steps * 1e3
-    # ---- check vs the oracle (the log's own stored Alh values, recomputed)
+    if a.dump_outputs:
+        # what the last timed call left in the caller's arrays
+        dump_outputs(a.dump_outputs,
+                     {"headers": outs[0].view(np.uint8).reshape(ntx, -1).copy(),
+                      "alh": outs[1].copy(), "status": outs[2].reshape(ntx, 1).copy()})
+    out = {"metric": "tx-log read-path validation (a14), %d records x %d entries, through the C "
+                     "ABI across %d device(s)" % (ntx, ne, K),
+           "value": round(ntx / (ms * 1e-3) / 1e6, 3), "unit": "M tx/s", "n_gpus": K, "api": "cabi",
+           "steps": a.steps, "warmup": a.warmup, "clock_prewarm": {"seconds": a.prewarm,
+                                                                   "calls": pre},
+           "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "strong",
+           "vs_baseline": None, "dtype": "u32",
+           "data": "synthetic v1 records (bench_workloads.txlog_records), sealed by the oracle, "
+                   "pinned host log and outputs", "full": a.full}
+    if not a.full:
+        print(json.dumps(out), flush=True)
+        md.close()
+        return
+    # ---- --full: check vs the oracle (the log's own stored Alh values, recomputed)
     tc = time.perf_counter()
     r = md.txlog_validate(raw, out=outs)
     o = orc.txlog_validate(raw)
@@ -840,20 +954,12 @@ def cabi_txlog(a):
                       "(tx.go:388-630) over the same log, all valid",
               "corrupted": corrupted, "seconds": round(time.perf_counter() - tc, 2)}
     md.close()
-    out = {"metric": "tx-log read-path validation (a14), %d records x %d entries, through the C "
-                     "ABI across %d device(s)" % (ntx, ne, K),
-           "value": round(ntx / (ms * 1e-3) / 1e6, 3), "unit": "M tx/s", "n_gpus": K, "api": "cabi",
-           "steps": a.steps, "warmup": a.warmup, "clock_prewarm": {"seconds": a.prewarm,
-                                                                   "calls": pre},
-           "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "strong",
-           "vs_baseline": None, "dtype": "u32",
-           "data": "synthetic v1 records (bench_workloads.txlog_records), sealed by the oracle, "
-                   "pinned host log and outputs",
+    out.update({
            "config": {"workload": "mh_multi_txlog_validate: the log cut at record boundaries, "
                                   "one part per device over its own PCIe link",
                       "log_bytes": int(raw.size), "records": ntx, "entries_per_record": ne},
            "log_GBps_incl_parse_and_h2d": round(raw.size / (ms * 1e-3) / 1e9, 2),
-           "cpu_baseline": None, "root_check": rcheck}
+           "cpu_baseline": None, "root_check": rcheck})
     print(json.dumps(out), flush=True)
     if not ok:
         print("root_check FAILED: %s" % json.dumps(rcheck), file=sys.stderr, flush=True)
@@ -1032,6 +1138,55 @@ def main():
     for c in ctxs:
         c.set_timing(False)
     elapsed = t1 - t0
+    if dist:
+        t = torch.tensor([elapsed], dtype=torch.float64,
+                         device="cpu" if backend == "gloo" else dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    if a.dump_outputs:
+        # what the caller of the last timed step received: that build's level
+        # array and root (and the tree's top over the N ranks' roots)
+        j = (a.steps - 1) % D
+        tag = "_rank%d" % rank if world > 1 else ""
+        o = {"levels" + tag: levels[j].view(-1, 32), "root" + tag: root[j].view(1, 32)}
+        if dist:
+            o["top_levels" + tag] = top_levels[j].view(-1, 32)
+            o["global_root" + tag] = groot[j].view(1, 32)
+        dump_outputs(a.dump_outputs, o, world)
+    out = {
+        "metric": "device-resident GiB/s hashed, htree build, 1M x 1KiB leaves" if a.config == "c2"
+        else "device-resident GiB/s hashed, htree build, 2^23 x 4KiB leaves per GPU (configs[3])",
+        "value": round(world * n * VAL / elapsed * a.steps / 2 ** 30, 3),
+        "unit": "GiB/s",
+        "n_gpus": world,
+        "process_group": {"backend": backend if dist else None,
+                          "world_size": dist.get_world_size() if dist else 1},
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "clock_prewarm": {"seconds": a.prewarm, "builds": pre,
+                          "note": "untimed full builds before the warmup steps (GPU clock ramp)"},
+        "ms_per_step": round(elapsed / a.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": a.scaling,
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": "synthetic (splitmix64 values generated in HBM, keys BE64(i))",
+        "full": a.full,
+    }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if comm_ctx is not None:
+            comm_ctx.close()
+        for c in ctxs:
+            c.close()
+        if dist:
+            dist.destroy_process_group()
+
+    if not a.full:
+        return finish()
+    # ---- --full: everything beside the headline figure, after the timed region
     if not a.timing_in_region:
         # the same steps (every in-flight stream) with the timing events on
         for c in ctxs:
@@ -1042,11 +1197,6 @@ def main():
         torch.cuda.synchronize(dev)
         for c in ctxs:
             c.set_timing(False)
-    if dist:
-        t = torch.tensor([elapsed], dtype=torch.float64,
-                         device="cpu" if backend == "gloo" else dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
     k_ms0, k_cnt0 = ctxs[0].timing("entries_fixed")
     # isolated launches (outside the timed region): ISO builds back to back on
     # ONE stream (a single BuildWith chain, i.e. --inflight 1), for the
@@ -1117,29 +1267,10 @@ def main():
         except (OSError, ValueError):
             traffic = None
 
-    total_bytes = world * n * VAL
-    value = total_bytes / elapsed * a.steps / 2 ** 30
     # the same algorithmic bytes over the measured time of one step (the
     # builds in flight overlap, so this is a sustained rate, not one launch)
     step_achieved = alg_bytes / (elapsed / a.steps) / 1e9
-    out = {
-        "metric": "device-resident GiB/s hashed, htree build, 1M x 1KiB leaves" if a.config == "c2"
-        else "device-resident GiB/s hashed, htree build, 2^23 x 4KiB leaves per GPU (configs[3])",
-        "value": round(value, 3),
-        "unit": "GiB/s",
-        "n_gpus": world,
-        "process_group": {"backend": backend if dist else None,
-                          "world_size": dist.get_world_size() if dist else 1},
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "clock_prewarm": {"seconds": a.prewarm, "builds": pre,
-                          "note": "untimed full builds before the warmup steps (GPU clock ramp)"},
-        "ms_per_step": round(elapsed / a.steps * 1e3, 4),
-        "higher_is_better": True,
-        "scaling": a.scaling,
-        "vs_baseline": None,
-        "dtype": "u32",
-        "data": "synthetic (splitmix64 values generated in HBM, keys BE64(i))",
+    out.update({
         "config": {"workload": "htree build (value SHA-256 + TxEntryDigest_v1_2 + leaf + all "
                                "levels), %d x %d B entries per GPU, %d B keys" % (n, VAL, KEY_LEN)
                    + ("; strong scaling: one %d-entry tree over %d GPUs" % (n * world, world)
@@ -1192,20 +1323,13 @@ def main():
                          "gib_per_s": round(n * VAL / (single_ms * 1e-3) / 2 ** 30, 2),
                          "note": "one BuildWith at a time (what one Go committer sees), "
                                  "50 builds back to back, no timing events"},
-    }
+    })
     if rank == 0 and world == 1 and not a.no_cpu_baseline and a.config == "c2":
         out["cpu_baseline"] = cpu_baseline(a.cpu_seconds)
     elif rank == 0:
         out["cpu_baseline"] = None
     out["root_check"] = rcheck
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if comm_ctx is not None:
-        comm_ctx.close()
-    for c in ctxs:
-        c.close()
-    if dist:
-        dist.destroy_process_group()
+    finish()
     if not rcheck["ok"]:
         print("root_check FAILED: %s" % json.dumps(rcheck), file=sys.stderr, flush=True)
         raise SystemExit(1)

@@ -3,6 +3,8 @@
 # VARIANTS="A=1 B=2 ..." style, each a space-free "NAME=VALUE[,NAME=VALUE]" or "base".
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
+# the table below prints roofline / single-build figures: those come with --full
+BENCH_ARGS="--full ${BENCH_ARGS}"
 mkdir -p gpurun_out
 for i in $(seq ${ROUNDS:-3}); do
   for v in $VARIANTS; do

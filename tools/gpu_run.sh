@@ -7,7 +7,8 @@
 # Steps:
 #   tests            every -m gpu test            tests:<expr>  only -k <expr>
 #   smoke            __graft_entry__.smoke()
-#   bench            the driver's default command (python bench.py)
+#   bench            the headline line with everything beside it (python bench.py --full); every
+#                    bench.py step below runs with --full: root check, kernel passes, roofline
 #   bench_cabi       bench.py --api cabi --gpus 1 (one-device RCCL clique)
 #   corrupt          bench.py with MH_BENCH_CORRUPT=0: must exit 1 (root check)
 #   corrupt_cabi     the same through --api cabi
@@ -62,36 +63,36 @@ for s in "$@"; do
     tests) step tests 1100 python -u -m pytest -m gpu -v --timeout 300 --timeout-method thread tests/ || exit 1 ;;
     tests:*) step tests_k 900 python -u -m pytest -m gpu -v --timeout 300 --timeout-method thread tests/ -k "${s#tests:}" || exit 1 ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" || exit 1 ;;
-    bench) step bench 400 python bench.py || exit 1 ;;
-    bench_cabi) step bench_cabi 300 python bench.py --api cabi --gpus 1 --steps 200 --warmup 5 || exit 1 ;;
+    bench) step bench 400 python bench.py --full || exit 1 ;;
+    bench_cabi) step bench_cabi 300 python bench.py --full --api cabi --gpus 1 --steps 200 --warmup 5 || exit 1 ;;
     corrupt)
-      MH_BENCH_CORRUPT=0 step corrupt 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline
+      MH_BENCH_CORRUPT=0 step corrupt 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline
       rc=$?; echo "corrupt exit $rc (want 1)"; [ $rc -eq 1 ] || exit 1 ;;
     corrupt_cabi)
-      MH_BENCH_CORRUPT=0 step corrupt_cabi 300 python bench.py --api cabi --gpus 1 --steps 20 --warmup 3
+      MH_BENCH_CORRUPT=0 step corrupt_cabi 300 python bench.py --full --api cabi --gpus 1 --steps 20 --warmup 3
       rc=$?; echo "corrupt_cabi exit $rc (want 1)"; [ $rc -eq 1 ] || exit 1 ;;
-    txcabi) step txcabi 400 python bench.py --api cabi --gpus 1 --config txlog --steps 100 --warmup 5 --prewarm 1 || exit 1 ;;
+    txcabi) step txcabi 400 python bench.py --full --api cabi --gpus 1 --config txlog --steps 100 --warmup 5 --prewarm 1 || exit 1 ;;
     txcabi_corrupt)
-      MH_BENCH_CORRUPT=0 step txcabi_corrupt 400 python bench.py --api cabi --gpus 1 --config txlog --steps 5 --warmup 1 --prewarm 0
+      MH_BENCH_CORRUPT=0 step txcabi_corrupt 400 python bench.py --full --api cabi --gpus 1 --config txlog --steps 5 --warmup 1 --prewarm 0
       rc=$?; echo "txcabi_corrupt exit $rc (want 1)"; [ $rc -eq 1 ] || exit 1 ;;
-    c3cabi) step c3cabi 400 python bench.py --api cabi --gpus 1 --config c3 --steps 10 --warmup 2 || exit 1 ;;
+    c3cabi) step c3cabi 400 python bench.py --full --api cabi --gpus 1 --config c3 --steps 10 --warmup 2 || exit 1 ;;
     dist2)
       MH_DIST_BACKEND=gloo HIP_VISIBLE_DEVICES=0 step dist2 400 python -m torch.distributed.run \
         --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29531 \
-        bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline || exit 1 ;;
+        bench.py --full --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline || exit 1 ;;
     dist8)  # 8 gloo ranks sharing GPU 0: the driver's N = 8 path (root check over 8 ranks) rehearsed
       MH_DIST_BACKEND=gloo HIP_VISIBLE_DEVICES=0 step dist8 500 python -m torch.distributed.run \
         --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29533 \
-        bench.py --gpus 8 --steps 20 --warmup 3 --prewarm 1 --no-cpu-baseline || exit 1 ;;
+        bench.py --full --gpus 8 --steps 20 --warmup 3 --prewarm 1 --no-cpu-baseline || exit 1 ;;
     dist2s|dist8s)  # --scaling strong: ONE 2^20-entry tree over N gloo ranks sharing GPU 0 (root vs the oracle)
       n=${s:4:1}
       MH_DIST_BACKEND=gloo HIP_VISIBLE_DEVICES=0 step "$s" 500 python -m torch.distributed.run \
         --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port 2953$n \
-        bench.py --gpus "$n" --scaling strong --steps 20 --warmup 3 --prewarm 1 --no-cpu-baseline || exit 1 ;;
+        bench.py --full --gpus "$n" --scaling strong --steps 20 --warmup 3 --prewarm 1 --no-cpu-baseline || exit 1 ;;
     dist8s_corrupt)  # the same with rank 5's shard corrupted: must exit 1
       MH_BENCH_CORRUPT=5 MH_DIST_BACKEND=gloo HIP_VISIBLE_DEVICES=0 step dist8s_corrupt 500 python -m torch.distributed.run \
         --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29539 \
-        bench.py --gpus 8 --scaling strong --steps 5 --warmup 1 --prewarm 0 --no-cpu-baseline
+        bench.py --full --gpus 8 --scaling strong --steps 5 --warmup 1 --prewarm 0 --no-cpu-baseline
       rc=$?; echo "dist8s_corrupt exit $rc (want 1)"; [ $rc -eq 1 ] || exit 1 ;;
     lanes_check)  # the range-checking k_txlog_lanes (make LANES_CHECK=1, built here over the snapshot's
       # library) under every tx-log test: any read outside the log fails the call
@@ -107,7 +108,7 @@ for s in "$@"; do
           echo "round $r threads $1 cliques $2 $line" | tee -a "$O/committers.txt"
         done
       done ;;
-    strong1) step strong1 300 python bench.py --scaling strong --steps 200 --warmup 5 --no-cpu-baseline || exit 1 ;;
+    strong1) step strong1 300 python bench.py --full --scaling strong --steps 200 --warmup 5 --no-cpu-baseline || exit 1 ;;
     wdist:*|wcorrupt:*)  # bench_workloads.py multi-rank lines, N gloo ranks sharing GPU 0
       w=$(echo "$s" | cut -d: -f2); n=$(echo "$s" | cut -d: -f3); kind=${s%%:*}
       corrupt=""; [ "$kind" = wcorrupt ] && corrupt="MH_BENCH_CORRUPT=1"
@@ -118,23 +119,23 @@ for s in "$@"; do
       if [ "$kind" = wcorrupt ]; then echo "$s exit $rc (want 1)"; [ $rc -eq 1 ] || exit 1
       else [ $rc -eq 0 ] || exit 1; fi ;;
     forcepg)  # the torch.distributed / RCCL code paths executed as one nccl rank
-      MH_DIST_FORCE_PG=1 step forcepg_c2 400 python bench.py --steps 200 --warmup 5 --no-cpu-baseline || exit 1
-      MH_DIST_FORCE_PG=1 step forcepg_c4 600 python bench.py --config c4 --steps 5 --warmup 1 --prewarm 0 --no-cpu-baseline || exit 1
+      MH_DIST_FORCE_PG=1 step forcepg_c2 400 python bench.py --full --steps 200 --warmup 5 --no-cpu-baseline || exit 1
+      MH_DIST_FORCE_PG=1 step forcepg_c4 600 python bench.py --full --config c4 --steps 5 --warmup 1 --prewarm 0 --no-cpu-baseline || exit 1
       MH_DIST_FORCE_PG=1 step forcepg_wc3 600 python bench_workloads.py --workload c3 --steps 5 --warmup 1 || exit 1
       MH_DIST_FORCE_PG=1 step forcepg_wc5 600 python bench_workloads.py --workload c5 --steps 5 --warmup 1 || exit 1 ;;
-    pgprof:*)  # kernel traces of bench.py per env variant (e.g. pgprof:base;MH_DIST_FORCE_PG=1) -> queue map
+    pgprof:*)  # kernel traces of bench.py --full per env variant (e.g. pgprof:base;MH_DIST_FORCE_PG=1) -> queue map
       vs="$(echo "${s#pgprof:}" | tr ';' ' ')"; i=0
       for v in $vs; do
         i=$((i+1)); envs=""; [ "$v" != base ] && envs=$(echo "$v" | tr ',' ' ')
         rm -rf "$O/pgprof_$i"
-        env $envs timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d "$O/pgprof_$i" -o run -- python3 bench.py --steps ${PG_STEPS:-200} --warmup 5 --no-cpu-baseline > "$O/pgprof_$i.out" 2> "$O/pgprof_$i.err" || { tail -5 "$O/pgprof_$i.err"; exit 1; }
+        env $envs timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d "$O/pgprof_$i" -o run -- python3 bench.py --full --steps ${PG_STEPS:-200} --warmup 5 --no-cpu-baseline > "$O/pgprof_$i.out" 2> "$O/pgprof_$i.err" || { tail -5 "$O/pgprof_$i.err"; exit 1; }
         { echo "# variant $v: $(tail -1 "$O/pgprof_$i.out" | cut -c1-160)"; python3 tools/queue_map.py "$O/pgprof_$i"; } | tee -a "$O/pgprof.txt"
         rm -rf "$O/pgprof_$i"
       done ;;
-    c4) step c4 600 python bench.py --config c4 --steps 5 --warmup 1 --prewarm 0 --no-cpu-baseline || exit 1 ;;
+    c4) step c4 600 python bench.py --full --config c4 --steps 5 --warmup 1 --prewarm 0 --no-cpu-baseline || exit 1 ;;
     prof)
       rm -rf "$O/prof"
-      step prof 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o run -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline || exit 1
+      step prof 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o run -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline || exit 1
       python3 tools/prof_summary.py "$O/prof/run_kernel_trace.csv" --steps 20 --warmup 5 > "$O/prof_summary.json" || exit 1
       gzip -f "$O/prof/run_kernel_trace.csv" ;;
     txlog) step txlog 300 ./tools/txlog_bench || exit 1 ;;
