@@ -44,6 +44,13 @@
                     back; chunked two-stream pipeline vs one chunk, next to the
                     plain pinned H2D rate of the same bytes (the PCIe bound) and
                     the oracle on 16 host threads.
+  --workload dualv1 the proof immudb serves: 10^5 ImmuStore.DualProof (v1, with
+                    LinearProof and LinearAdvanceProof) over a 2^20-append ahtree
+                    whose BlTxID lags each tx by 1-4 txs, generated and marshalled
+                    as schema.DualProof on the device from the resident dLog and a
+                    resident Alh / innerHash window (mh_dev_dual_proof_pb_batch:
+                    sizes pass, scan, write pass); proofs/s and output GiB/s; a
+                    sample checked against the CPU restatement of the tests.
 
 Each prints one JSON line.  bench.py stays the driver's headline benchmark.
 
@@ -408,7 +415,7 @@ def distributed_main(a):
 def make_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--workload", choices=["c3", "c5", "c2e2e", "txlog", "commit", "wire", "ragged", "document",
-                                          "values", "c3range"],
+                                          "values", "c3range", "dualv1"],
                    required=True)
     p.add_argument("--logs", action="store_true",
                    help="c3: also write the pLog / cLog appendable records (8(f) row 4)")
@@ -431,6 +438,8 @@ def make_parser():
     p.add_argument("--no-check", action="store_true", help="ragged: skip the oracle check")
     p.add_argument("--docs", type=int, default=8192, help="document: documents")
     p.add_argument("--doc-entries", type=int, default=64, help="document: entries per tx")
+    p.add_argument("--v1-proofs", type=int, default=10 ** 5, help="dualv1: header pairs")
+    p.add_argument("--v1-depth", type=int, default=20, help="dualv1: log2 of the appends")
     return p
 
 
@@ -1531,6 +1540,89 @@ def run_single(a):
                            "statuses down; the bench tree's payloads are not these headers' Alh, "
                            "so the verdicts are 'inclusion not valid' (every kernel still runs)"},
                "sample_vs_oracle": bool(ok)}
+
+    elif a.workload == "dualv1":
+        from immustore_amd.txlayer import TX_HEADER
+        P, W = a.v1_proofs, 1 << a.v1_depth
+        rng = np.random.default_rng(21)
+        # the resident state of a server: the dLog of W appends and the Alh /
+        # innerHash of every tx (random digests: the generator hashes nothing)
+        pay = torch.empty(W * 32, dtype=torch.uint8, device=dev)
+        N.check(L.mh_dev_fill_random(ctx.handle, pay.data_ptr(), pay.numel(), 21))
+        dlog = torch.empty(m.nodes_upto(W) * 32, dtype=torch.uint8, device=dev)
+        N.check(L.mh_dev_ahtree_append_batch(ctx.handle, dlog.data_ptr(), 0, pay.data_ptr(), W, 32,
+                                             None))
+        inner = torch.empty(W * 32, dtype=torch.uint8, device=dev)
+        N.check(L.mh_dev_fill_random(ctx.handle, inner.data_ptr(), inner.numel(), 22))
+        alh = pay  # tx k's Alh is leaf k's payload
+        tid = rng.integers(2, W + 1, P).astype(np.uint64)
+        sid = (rng.random(P) * tid).astype(np.uint64) + 1
+        sid = np.minimum(sid, tid)
+
+        def hdrs(ids):
+            h = np.zeros(P, TX_HEADER)
+            h["id"] = ids
+            lag = ids.astype(np.int64) - 1 - (ids.astype(np.int64) % 4)  # BlTxID 1-4 txs behind
+            h["bl_tx_id"] = np.maximum(lag, 0).astype(np.uint64)
+            h["ts"] = 1666885208 + ids.astype(np.int64)
+            h["version"] = 1
+            h["nentries"] = 16
+            for f in ("bl_root", "prev_alh", "eh"):
+                h[f] = rng.integers(0, 256, (P, 32), dtype=np.uint8)
+            return torch.from_numpy(h.view(np.uint8).reshape(-1)).to(dev)
+
+        hs, ht = hdrs(sid), hdrs(tid)
+        off = torch.empty(P + 1, dtype=torch.int64, device=dev)
+        st = torch.empty(P, dtype=torch.int32, device=dev)
+        scratch = torch.empty(L.mh_pb_dual_scratch_size(P), dtype=torch.uint8, device=dev)
+
+        def call(phase, out_ptr, cap):
+            N.check(L.mh_dev_dual_proof_pb_batch(ctx.handle, phase, dlog.data_ptr(), W, P,
+                                                 hs.data_ptr(), ht.data_ptr(), None, 1, W,
+                                                 alh.data_ptr(), inner.data_ptr(), out_ptr, cap,
+                                                 off.data_ptr(), st.data_ptr(), scratch.data_ptr()))
+
+        call(1, None, 0)
+        sync()
+        total = int(off[P].item())
+        outb = torch.empty(total, dtype=torch.uint8, device=dev)
+
+        def step_v1():
+            call(3, outb.data_ptr(), total)
+
+        prewarm(step_v1, sync, a.prewarm)
+        td = timed_k(ctx, step_v1, a.steps, a.warmup, sync)
+        kd = {k: ctx.timing(k)[0] / (a.steps + a.warmup) for k in ("pb_dual1_size",
+                                                                   "pb_dual1_write")}
+        assert int(st.abs().sum().item()) == 0
+        # sample check against the CPU restatement (tests/dual_v1_gen_util.py: the
+        # oracle's ahtree walks over the device dLog + the protobuf runtime)
+        sys.path.insert(0, os.path.join(HERE, "oracle"))
+        sys.path.insert(0, os.path.join(HERE, "tests"))
+        import oracle as O
+        import dual_v1_gen_util as U
+        o = O.AHtree(1)
+        o.dlog = dlog.view(-1, 32).cpu().numpy()
+        o.size = W
+        alh_h, inner_h = alh.view(-1, 32).cpu().numpy(), inner.view(-1, 32).cpu().numpy()
+        hs_h = hs.cpu().numpy().view(TX_HEADER)
+        ht_h = ht.cpu().numpy().view(TX_HEADER)
+        offs = off.cpu().numpy()
+        ob = outb.cpu().numpy()
+        ok = True
+        for k in [int(x) for x in rng.integers(0, P, 200)]:
+            est, parts = U.go_dual_proof_parts(hs_h[k], ht_h[k], b"", o, 1, alh_h, inner_h)
+            ok &= est == 0 and U.dual_v1_marshal(parts) == ob[offs[k]:offs[k + 1]].tobytes()
+        sizes = np.diff(offs)
+        out = {"metric": "DualProof (v1) protobuf messages built on the device, %d x (2^%d tree, "
+                         "BlTxID 1-4 txs behind)" % (P, a.v1_depth),
+               "value": round(P / td / 1e6, 3), "unit": "M proofs/s",
+               "ms_per_step": round(td * 1e3, 3), "bytes_out": total,
+               "out_GiBps": round(total / td / 2 ** 30, 2),
+               "message_bytes": {"min": int(sizes.min()), "mean": round(float(sizes.mean()), 1),
+                                 "max": int(sizes.max())},
+               "kernel_ms": {k: round(v, 3) for k, v in kd.items()},
+               "sample_vs_restatement": bool(ok)}
 
     out["workload"] = a.workload
     ctx.close()

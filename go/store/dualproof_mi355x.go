@@ -1,0 +1,141 @@
+//go:build mi355x
+
+// The MI355X build's batch form of ImmuStore.DualProof (immustore.go:2394-2463,
+// with LinearProof :2472-2510 and LinearAdvanceProof :2514-2562) followed by
+// DualProofToProto + Marshal (pkg/api/schema/database_protoconv.go:131-211):
+// the answers of a batch of VerifiableGet / VerifiableSet / VerifiableTxById
+// requests (pkg/database/database.go:805,881) generated and encoded in one
+// device pass over a dLog kept resident beside the store's aht, instead of one
+// walk over the tree and the tx log per proof.  Uncompiled in the build image
+// (no Go toolchain); see go/README.md.
+package store
+
+/*
+#cgo CFLAGS: -I${SRCDIR}/../../third_party/immustore_amd/include
+#cgo LDFLAGS: -L${SRCDIR}/../../third_party/immustore_amd -limmustore_merkle -Wl,-rpath,${SRCDIR}/../../third_party/immustore_amd
+#include <stdlib.h>
+#include "immustore_merkle.h"
+*/
+import "C"
+
+import (
+	"crypto/sha256"
+	"runtime"
+	"unsafe"
+
+	"github.com/codenotary/immudb/embedded/internal/mi355x"
+)
+
+// ProofTree is the store's aht mirrored on the device: the caller appends the
+// same Alh values the store appends to s.aht (immustore.go:1198-1232,
+// :1764-1770), in the same order.
+type ProofTree struct {
+	t *C.mh_ahtree
+}
+
+func NewProofTree() (*ProofTree, error) {
+	p, err := mi355x.Context()
+	if err != nil {
+		return nil, err
+	}
+	pt := &ProofTree{}
+	if st := C.mh_ahtree_new((*C.mh_ctx)(p), &pt.t); st != C.MH_OK {
+		return nil, mapErr(st)
+	}
+	runtime.SetFinalizer(pt, func(pt *ProofTree) { C.mh_ahtree_free(pt.t) })
+	return pt, nil
+}
+
+// AppendBatch appends the Alh of every tx of a run, as aht.Append(alh[:]) does
+// one.
+func (pt *ProofTree) AppendBatch(alhs [][sha256.Size]byte) error {
+	if len(alhs) == 0 {
+		return nil
+	}
+	return mapErr(C.mh_ahtree_append_batch(pt.t, (*C.uint8_t)(unsafe.Pointer(&alhs[0][0])),
+		C.uint64_t(len(alhs)), C.uint32_t(sha256.Size), nil))
+}
+
+// mapProofErr: DualProof's own sentinel beside the store-wide mapping.
+func mapProofErr(st C.int) error {
+	if st == C.MH_ERR_SOURCE_TX_NEWER {
+		return ErrSourceTxNewerThanTargetTx // immustore.go:101
+	}
+	return mapErr(st)
+}
+
+func packHeaders(hdrs []*TxHeader, blob *[]byte) []C.mh_tx_header {
+	out := make([]C.mh_tx_header, len(hdrs)+1)
+	for i, h := range hdrs {
+		o := &out[i]
+		o.id, o.ts, o.bl_tx_id = C.uint64_t(h.ID), C.int64_t(h.Ts), C.uint64_t(h.BlTxID)
+		o.version, o.nentries = C.uint32_t(h.Version), C.uint32_t(h.NEntries)
+		for k := 0; k < sha256.Size; k++ {
+			o.bl_root[k], o.prev_alh[k], o.eh[k] = C.uint8_t(h.BlRoot[k]), C.uint8_t(h.PrevAlh[k]), C.uint8_t(h.Eh[k])
+		}
+		if h.Metadata != nil { // tx.go:483-501: nil when the stored length is 0
+			md := h.Metadata.Bytes()
+			o.md_off, o.md_len = C.uint32_t(len(*blob)), C.uint32_t(len(md))
+			*blob = append(*blob, md...)
+		}
+	}
+	return out
+}
+
+// DualProofBatch is ImmuStore.DualProof(src[p], tgt[p]) marshalled as
+// schema.DualProof, for every pair.  alh / inner are the digest window: Alh()
+// and innerHash() of the txs firstTx .. firstTx + len(alh) - 1 (the linear
+// parts are runs of them; the tree holds only SHA-256(0x00 || Alh)).  msgs[p]
+// is the message, or nil with errs[p] the error DualProof would have returned:
+// ErrIllegalArguments, ErrSourceTxNewerThanTargetTx, ErrCorruptedTxData,
+// ErrTxNotFound (a tx outside the window), ErrCorruptedData,
+// ahtree.ErrUnexistentData as a status error.
+func (pt *ProofTree) DualProofBatch(src, tgt []*TxHeader, firstTx uint64,
+	alh, inner [][sha256.Size]byte) (msgs [][]byte, errs []error, err error) {
+	n := len(src)
+	if len(tgt) != n || len(inner) != len(alh) {
+		return nil, nil, ErrIllegalArguments
+	}
+	if n == 0 {
+		return nil, nil, nil
+	}
+	for p := 0; p < n; p++ {
+		if src[p] == nil || tgt[p] == nil { // immustore.go:2395-2397
+			return nil, nil, ErrIllegalArguments
+		}
+	}
+	blob := make([]byte, 0, 64)
+	sh, th := packHeaders(src, &blob), packHeaders(tgt, &blob)
+	blob = append(blob, 0)
+	var ap, ip *C.uint8_t
+	if len(alh) > 0 {
+		ap, ip = (*C.uint8_t)(unsafe.Pointer(&alh[0][0])), (*C.uint8_t)(unsafe.Pointer(&inner[0][0]))
+	}
+	off := make([]uint64, n+1)
+	status := make([]int32, n)
+	out := make([]byte, 4096*n)
+	for try := 0; try < 2; try++ {
+		st := C.mh_ahtree_dual_proof_pb_batch(pt.t, C.uint64_t(n), &sh[0], &th[0],
+			(*C.uint8_t)(unsafe.Pointer(&blob[0])), C.uint64_t(len(blob)-1), C.uint64_t(firstTx),
+			C.uint64_t(len(alh)), ap, ip, (*C.uint8_t)(unsafe.Pointer(&out[0])), C.uint64_t(len(out)),
+			(*C.uint64_t)(unsafe.Pointer(&off[0])), (*C.int32_t)(unsafe.Pointer(&status[0])))
+		if st == C.MH_ERR_BUFFER_TOO_SMALL && try == 0 {
+			out = make([]byte, off[n]+1) // the size query: off[n] is the total
+			continue
+		}
+		if st != C.MH_OK {
+			return nil, nil, mapErr(st)
+		}
+		break
+	}
+	msgs = make([][]byte, n)
+	errs = make([]error, n)
+	for p := 0; p < n; p++ {
+		if status[p] != 0 {
+			errs[p] = mapProofErr(C.int(status[p]))
+			continue
+		}
+		msgs[p] = out[off[p]:off[p+1]]
+	}
+	return msgs, errs, nil
+}

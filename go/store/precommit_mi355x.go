@@ -47,6 +47,10 @@ func mapErr(st C.int) error {
 		return ErrCorruptedTxDataMaxKeyLenExceeded
 	case C.MH_ERR_CORRUPTED_UNKNOWN_VERSION:
 		return ErrCorruptedTxDataUnknownHeaderVersion
+	case C.MH_ERR_CORRUPTED_TX_DATA:
+		return ErrCorruptedTxData // immustore.go:71
+	case C.MH_ERR_TX_NOT_FOUND:
+		return ErrTxNotFound // immustore.go:85
 	}
 	return mi355x.Status(int(st))
 }

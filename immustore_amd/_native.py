@@ -39,6 +39,8 @@ MH_ERR_INVALID_PROOF = 20
 MH_ERR_UNSUPPORTED_TX_VERSION = 21
 MH_ERR_INVALID_PROOF_ENTRY = 22
 MH_ERR_COLLECTIVE = 23
+MH_ERR_CORRUPTED_TX_DATA = 24
+MH_ERR_TX_NOT_FOUND = 25
 
 MH_AHT_INCLUSION = 0
 MH_AHT_CONSISTENCY = 1
@@ -151,6 +153,10 @@ class ErrCollective(MerkleError):
     """RCCL unavailable or a collective failed (mh_multi_*)"""
 
 
+class ErrTxNotFound(MerkleError):
+    """store.ErrTxNotFound (immustore.go:85)"""
+
+
 class HipError(MerkleError):
     pass
 
@@ -179,6 +185,8 @@ _ERRORS = {
     MH_ERR_UNSUPPORTED_TX_VERSION: ErrUnsupportedTxVersion,
     MH_ERR_INVALID_PROOF_ENTRY: ErrInvalidProofEntry,
     MH_ERR_COLLECTIVE: ErrCollective,
+    MH_ERR_CORRUPTED_TX_DATA: ErrCorruptedTxData,
+    MH_ERR_TX_NOT_FOUND: ErrTxNotFound,
 }
 
 vp = C.c_void_p
@@ -248,6 +256,11 @@ SIGNATURES = {
     "mh_ahtree_dual_proof_v2_pb_batch": (i32, [vp, u64, vp, vp, u8p, u64, u8p, u64, vp, vp]),
     "mh_dev_htree_inclusion_proof_pb_batch": (i32, [vp, i32, u8p, u64, u64, vp, u8p, u64, vp, vp, vp]),
     "mh_dev_dual_proof_v2_pb_batch": (i32, [vp, i32, u8p, u64, u64, vp, vp, u8p, u8p, u64, vp, vp, vp]),
+    "mh_pb_dual_scratch_size": (u64, [u64]),
+    "mh_ahtree_dual_proof_pb_batch": (i32, [vp, u64, vp, vp, u8p, u64, u64, u64, u8p, u8p, u8p, u64,
+                                            vp, vp]),
+    "mh_dev_dual_proof_pb_batch": (i32, [vp, i32, u8p, u64, u64, vp, vp, u8p, u64, u64, u8p, u8p,
+                                         u8p, u64, vp, vp, vp]),
     "mh_ahtree_append_batch_logs": (i32, [vp, u8p, u64, u32, u64, u8p, u8p, u8p]),
     "mh_dev_ahtree_append_batch_logs": (i32, [vp, u8p, u64, u8p, u64, u32, u64, u8p, u8p, u8p]),
     "mh_dev_ahtree_log_records": (i32, [vp, u8p, u64, u32, u64, u8p, u8p]),

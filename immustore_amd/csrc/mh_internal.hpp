@@ -384,4 +384,12 @@ hipError_t launch_pb_dual_v2(hipStream_t st, Timer *tm, int phase, const uint8_t
 hipError_t launch_pb_inclusion(hipStream_t st, Timer *tm, int phase, const uint8_t *levels,
                                uint64_t w, uint64_t n, const uint64_t *leaf, uint8_t *out,
                                uint64_t out_cap, uint64_t *off, int32_t *status, uint8_t *scratch);
+// DualProof (v1): scratch = pb_dual_v1_scratch_bytes(n); alh / inner = the digest
+// window of txs first_tx .. first_tx + count - 1 (device, 16-byte aligned)
+uint64_t pb_dual_v1_scratch_bytes(uint64_t n);
+hipError_t launch_pb_dual_v1(hipStream_t st, Timer *tm, int phase, const uint8_t *dlog,
+                             uint64_t size, uint64_t n, const MhTxHeader *src,
+                             const MhTxHeader *tgt, const uint8_t *md_blob, uint64_t first_tx,
+                             uint64_t count, const uint8_t *alh, const uint8_t *inner, uint8_t *out,
+                             uint64_t out_cap, uint64_t *off, int32_t *status, uint8_t *scratch);
 }  // namespace mh

@@ -780,4 +780,381 @@ hipError_t launch_pb_inclusion(hipStream_t st, Timer *tm, int phase, const uint8
     return hipSuccess;
 }
 
+// ------------------------------------------------------------ DualProof (v1)
+//   DualProof           schema.proto:388-434   DualProofToProto          database_protoconv.go:131-142
+//   LinearProof                                LinearProofToProto        database_protoconv.go:195-201
+//   LinearAdvanceProof                         LinearAdvanceProofToProto database_protoconv.go:203-211
+//   proofs of ImmuStore.DualProof / LinearProof / LinearAdvanceProof     immustore.go:2394-2562
+//
+// The answer VerifiableGet / VerifiableSet / VerifiableTxById send.  Its
+// ahtree parts are index walks over the dLog as in DualProofV2; its linear
+// parts are Alh / innerHash values of whole runs of txs, which the dLog does
+// not hold (a leaf is SHA-256(0x00 || Alh)): they are gathered from the
+// caller's digest window (first_tx, count, alh, inner: what mh_tx_alh_batch
+// wrote for txs first_tx .. first_tx + count - 1).  Nothing is hashed here.
+//
+// Messages run from a few hundred bytes to hundreds of KiB, so one wave
+// takes one message in both passes.  The checks, the header sizes and the
+// three top-level walks are wave-uniform (every lane repeats them: for short
+// messages the wave does one lane's work); only the advance part is spread,
+// the size pass putting the term counts of the a1 - a0 - 1 nested inclusion
+// proofs on the lanes (lanes over k, wave sum).  The write pass
+// writes every run of 34-byte records with a lane per record (wave_run34)
+// and the nested proofs of the advance part a round of up to 64 at a time,
+// lane per proof for the walk, wave prefix sum for the starts, lane per
+// record for the stores.  Node indices are 64-bit throughout: one writer
+// for every tree size.
+struct PbDual1 {
+    PbHdr s, t;
+    uint64_t bl = 0;          // tgt.BlTxID: the tree size of every ahtree proof
+    uint64_t ls = 0, lt = 0;  // LinearProof(ls, lt)
+    uint64_t a0 = 0, a1 = 0;  // LinearAdvanceProof(a0, a1, bl)
+    bool incl = false, cons = false, last = false, adv = false;
+    int32_t st = MH_OK;
+};
+
+// what the size pass leaves for the writer
+struct PbDual1Parts {
+    uint64_t adv_body;    // LinearAdvanceProof message length
+    uint32_t ni, nc, nl;  // InclusionProof / ConsistencyProof / LastInclusionProof terms
+    uint32_t pad;
+};
+
+// txs lo .. hi (lo <= hi) are in the digest window
+__device__ __forceinline__ bool pb_in_window(uint64_t first, uint64_t count, uint64_t lo, uint64_t hi) {
+    return count && lo >= first && hi - first < count;
+}
+
+// The checks of ImmuStore.DualProof in Go's order; the first that fires is
+// the status.  src.ID == 0 is refused (the store holds no tx 0; Go would walk
+// the tree from leaf 0), as for DualProofV2.
+__device__ inline PbDual1 pb_dual1(const MhTxHeader &src, const MhTxHeader &tgt,
+                                   const uint8_t *md_blob, uint64_t size, uint64_t first,
+                                   uint64_t count) {
+    PbDual1 d;
+    if (src.id == 0) { d.st = MH_ERR_ILLEGAL_ARGUMENTS; return d; }
+    if (src.id > tgt.id) { d.st = MH_ERR_SOURCE_TX_NEWER; return d; }
+    d.bl = tgt.bl_tx_id;
+    // (*AHtree).InclusionProof / ConsistencyProof (ahtree.go:525-545, 579-597):
+    // i <= j holds at every call below; j beyond the tree is ErrUnexistentData
+    d.incl = src.id < d.bl;
+    if (d.incl && d.bl > size) { d.st = MH_ERR_UNEXISTENT_DATA; return d; }
+    if (src.bl_tx_id > d.bl) { d.st = MH_ERR_CORRUPTED_TX_DATA; return d; }  // immustore.go:2416
+    d.cons = src.bl_tx_id > 0;
+    if (d.cons && d.bl > size) { d.st = MH_ERR_UNEXISTENT_DATA; return d; }
+    d.last = d.bl > 0;
+    if (d.last) {
+        if (!pb_in_window(first, count, d.bl, d.bl)) { d.st = MH_ERR_TX_NOT_FOUND; return d; }
+        if (d.bl > size) { d.st = MH_ERR_UNEXISTENT_DATA; return d; }
+    }
+    d.ls = src.id > d.bl ? src.id : d.bl;  // immustore.go:2446, :2472-2475
+    d.lt = tgt.id;
+    if (d.ls > d.lt) { d.st = MH_ERR_SOURCE_TX_NEWER; return d; }
+    if (!pb_in_window(first, count, d.ls, d.lt)) { d.st = MH_ERR_TX_NOT_FOUND; return d; }
+    d.a0 = src.bl_tx_id;                   // immustore.go:2452-2456, :2514-2521
+    d.a1 = src.id < d.bl ? src.id : d.bl;
+    if (d.a1 < d.a0) { d.st = MH_ERR_SOURCE_TX_NEWER; return d; }
+    d.adv = d.a1 - d.a0 > 1;
+    if (d.adv && !pb_in_window(first, count, d.a0 + 1, d.a1)) { d.st = MH_ERR_TX_NOT_FOUND; return d; }
+    d.s = pb_header(src, md_blob);
+    if (d.s.st) { d.st = d.s.st; return d; }
+    d.t = pb_header(tgt, md_blob);
+    if (d.t.st) { d.st = d.t.st; return d; }
+    return d;
+}
+
+__device__ __forceinline__ uint64_t framed64(uint64_t body) { return 1 + vlen(body) + body; }
+
+// LinearProof message length: sourceTxId, TargetTxId (both > 0) and lt - ls + 1 terms
+__device__ __forceinline__ uint64_t pb_linear_body(uint64_t ls, uint64_t lt) {
+    return 2 + vlen(ls) + vlen(lt) + 34 * (lt - ls + 1);
+}
+
+__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
+#pragma unroll
+    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+// Size pass: one wave per message, 4 per block.  Reads the headers and their
+// metadata only.
+__global__ __launch_bounds__(256) void k_pb_dual1_size(uint64_t size, uint64_t n,
+                                                       const MhTxHeader *__restrict__ src,
+                                                       const MhTxHeader *__restrict__ tgt,
+                                                       const uint8_t *__restrict__ md_blob,
+                                                       uint64_t first, uint64_t count,
+                                                       uint64_t *__restrict__ sizes,
+                                                       PbDual1Parts *__restrict__ parts,
+                                                       int32_t *__restrict__ status) {
+    const uint64_t p = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (p >= n) return;  // wave-uniform
+    const MhTxHeader &S = src[p], &T = tgt[p];
+    const PbDual1 d = pb_dual1(S, T, md_blob, size, first, count);
+    auto none = [](uint32_t, uint64_t) {};
+    PbDual1Parts pt = {0, 0, 0, 0, 0};
+    uint64_t s = 0;
+    if (!d.st) {
+        if (d.incl) pt.ni = ahtree_walk(false, S.id, d.bl, none);
+        if (d.cons) pt.nc = ahtree_walk(true, S.bl_tx_id, d.bl, none);
+        if (d.last) pt.nl = ahtree_walk(false, d.bl, d.bl, none);
+        s = framed(d.s.body) + framed(d.t.body) + 34ull * (pt.ni + pt.nc + 1 + pt.nl) +
+            framed64(pb_linear_body(d.ls, d.lt));
+        if (d.adv) {  // nested proofs k = a0+1 .. a1-1, lanes over k
+            const uint64_t np = d.a1 - d.a0 - 1;
+            uint64_t nested = 0;
+            for (uint64_t q = lane; q < np; q += 64)
+                nested += framed64(34ull * ahtree_walk(false, d.a0 + 1 + q, d.bl, none));
+            pt.adv_body = 34 * (d.a1 - d.a0) + wave_sum_u64(nested);
+            s += framed64(pt.adv_body);
+        }
+    }
+    if (lane == 0) {
+        sizes[p] = s;
+        parts[p] = pt;
+        status[p] = d.st;
+    }
+}
+
+// cnt records of 34 bytes, lane per record, two gathers per lane in flight.
+// at(r, dst, tag) gives the 32 source bytes of record r (16-byte aligned;
+// nullptr: zeros), where it goes and its tag; a lane sees its r ascending.
+// Called by the whole wave.
+template <class At>
+__device__ __forceinline__ void wave_run34(uint64_t cnt, int lane, At &&at) {
+    for (uint64_t r0 = 0; r0 < cnt; r0 += 128) {
+        uint32_t x[2][8], tag[2] = {0, 0};
+        uint8_t *pr[2] = {nullptr, nullptr};
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            const uint64_t r = r0 + 64 * u + lane;
+            if (r < cnt) {
+                const uint8_t *s = at(r, pr[u], tag[u]);
+                if (s) {
+                    load_node(s, x[u]);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 8; k++) x[u][k] = 0;
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 2; u++)
+            if (pr[u]) put_rec34_as<1>(pr[u], tag[u], x[u]);
+    }
+}
+
+// A/B on MI355X (profiles/ab_dualv1_idxcap.txt; 10^5 messages of ~3 KB over a
+// 2^20-append tree): 2048 entries (17 KB of LDS per one-wave block, 9 waves per
+// CU) 3.04 ms, 512 entries 2.17 ms.  Long advance parts take more rounds for it.
+#ifndef MH_PB1_IDXCAP
+#define MH_PB1_IDXCAP 512
+#endif
+constexpr uint32_t kIdx1Cap = MH_PB1_IDXCAP;
+// one round holds min(64, kIdx1Cap / maxc) nested proofs of up to maxc <= 64
+// terms each; the top-level lists (<= 64 + 130 + 64 terms) share the array
+static_assert(kIdx1Cap >= 320, "the top-level lists must fit");
+struct Wave1Lds {
+    uint64_t idx[kIdx1Cap];  // dLog node indices
+    uint64_t base[64];       // first record of nested proof `lane`
+    uint32_t pre[65];        // exclusive prefix of the nested term counts
+};
+
+__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = (uint32_t)__shfl_up((int)v, d, 64);
+        if (lane >= d) v += y;
+    }
+    return v;
+}
+
+// Write pass: one wave (one block) per message.
+__global__ __launch_bounds__(64) void k_pb_dual1_write(const uint8_t *__restrict__ dlog,
+                                                       uint64_t size, uint64_t n,
+                                                       const MhTxHeader *__restrict__ src,
+                                                       const MhTxHeader *__restrict__ tgt,
+                                                       const uint8_t *__restrict__ md_blob,
+                                                       uint64_t first, uint64_t count,
+                                                       const uint8_t *__restrict__ alh,
+                                                       const uint8_t *__restrict__ inner,
+                                                       const uint64_t *__restrict__ off,
+                                                       const PbDual1Parts *__restrict__ parts,
+                                                       uint8_t *__restrict__ out, uint64_t out_cap,
+                                                       int32_t *__restrict__ status) {
+    __shared__ Wave1Lds L;
+    const uint64_t p = blockIdx.x;
+    const int lane = threadIdx.x;
+    // everything up to the record loops is wave-uniform
+    if (p >= n || status[p] != MH_OK) return;
+    if (off[p + 1] > out_cap) {
+        if (lane == 0) status[p] = MH_ERR_BUFFER_TOO_SMALL;
+        return;
+    }
+    const MhTxHeader &S = src[p], &T = tgt[p];
+    const PbDual1 d = pb_dual1(S, T, md_blob, size, first, count);
+    const PbDual1Parts pt = parts[p];
+    const uint32_t ni = pt.ni, nc = pt.nc, nl = pt.nl;
+    const uint32_t nrec = ni + nc + 1 + nl;  // inclusion | consistency | TargetBlTxAlh | last
+    if (d.st || nrec > kIdx1Cap) {           // phase 2 without its phase 1: never seen
+        if (lane == 0) status[p] = MH_ERR_ILLEGAL_STATE;
+        return;
+    }
+    uint8_t *o = out + off[p];
+    const uint32_t hs = framed(d.s.body);
+    uint8_t *rec = o + hs + framed(d.t.body);
+    uint8_t *lin = rec + 34ull * nrec;
+    const uint64_t lin_body = pb_linear_body(d.ls, d.lt);
+    uint8_t *lin_terms = lin + 1 + vlen(lin_body) + 2 + vlen(d.ls) + vlen(d.lt);
+    uint8_t *adv = lin + framed64(lin_body);
+
+    // the byte streams: the two headers on lanes 0 and 1, the sub-message
+    // prefixes on lane 2
+    if (lane < 2) {
+        const MhTxHeader &H = lane ? T : S;
+        ByteWriter bw(lane ? o + hs : o);
+        put_header(bw, lane ? 0x12 : 0x0a, H, lane ? d.t : d.s, md_blob);
+        bw.finish();
+    } else if (lane == 2) {
+        ByteWriter bw(lin);
+        bw.put8(0x3a);
+        bw.varint(lin_body);
+        bw.put8(0x08);
+        bw.varint(d.ls);
+        bw.put8(0x10);
+        bw.varint(d.lt);
+        bw.finish();
+        if (d.adv) {
+            ByteWriter ba(adv);
+            ba.put8(0x42);
+            ba.varint(pt.adv_body);
+            ba.finish();
+        }
+    }
+
+    // the three top-level walks on lanes 0..2, proof order into L.idx
+    bool bad = false;
+    if (lane < 3) {
+        const bool c1 = lane == 1;
+        const uint64_t i = lane == 0 ? S.id : c1 ? S.bl_tx_id : d.bl;
+        const uint32_t cnt = lane == 0 ? ni : c1 ? nc : nl;
+        const uint32_t at = lane == 0 ? 0 : c1 ? ni : ni + nc + 1;
+        if (cnt) {
+            const uint32_t c = ahtree_walk(c1, i, d.bl, [&](uint32_t q, uint64_t node) {
+                if (q < cnt) L.idx[at + cnt - 1 - q] = node;
+            });
+            bad = c != cnt;
+        }
+    }
+    __syncthreads();
+    if (__any(bad)) {  // size pass and writer disagree: never seen; no index is read
+        if (lane == 0) status[p] = MH_ERR_ILLEGAL_STATE;
+        return;
+    }
+    wave_run34(nrec, lane, [&](uint64_t r, uint8_t *&dst, uint32_t &tag) -> const uint8_t * {
+        dst = rec + 34 * r;
+        if (r == ni + nc) {  // TargetBlTxAlh: always present, zeros without a BlTxID
+            tag = 0x2a;
+            return d.last ? alh + 32 * (d.bl - first) : nullptr;
+        }
+        tag = r < ni ? 0x1a : r < ni + nc ? 0x22 : 0x32;
+        return dlog + 32 * L.idx[r];
+    });
+    // LinearProof.terms: Alh(ls), innerHash(ls + 1 .. lt)
+    wave_run34(d.lt - d.ls + 1, lane, [&](uint64_t q, uint8_t *&dst, uint32_t &tag) {
+        dst = lin_terms + 34 * q;
+        tag = 0x1a;
+        return (q ? inner : alh) + 32 * (d.ls + q - first);
+    });
+    if (!d.adv) return;
+
+    // LinearAdvanceProof.linearProofTerms: Alh(a0 + 1), innerHash(a0 + 2 .. a1)
+    const uint64_t na = d.a1 - d.a0;
+    uint8_t *adv_terms = adv + 1 + vlen(pt.adv_body);
+    wave_run34(na, lane, [&](uint64_t q, uint8_t *&dst, uint32_t &tag) {
+        dst = adv_terms + 34 * q;
+        tag = 0x0a;
+        return (q ? inner : alh) + 32 * (d.a0 + 1 + q - first);
+    });
+    // LinearAdvanceProof.inclusionProofs: InclusionProof(k, bl), k = a0+1 .. a1-1
+    uint8_t *cur = adv_terms + 34 * na;
+    const uint32_t maxc = (uint32_t)bits_len(d.bl - 1);  // >= 1 (bl >= 2); terms of one walk
+    const uint32_t P = min(64u, kIdx1Cap / maxc);        // proofs per round
+    for (uint64_t k0 = 0; k0 < na - 1; k0 += P) {
+        const bool on = (uint32_t)lane < P && k0 + lane < na - 1;
+        __syncthreads();  // the previous round's records are out of L
+        uint32_t c = 0;
+        if (on)  // walk order into the lane's slot
+            c = ahtree_walk(false, d.a0 + 1 + k0 + lane, d.bl, [&](uint32_t q, uint64_t node) {
+                if (q < maxc) L.idx[lane * maxc + q] = node;
+            });
+        if (c > maxc) {  // cannot happen: one term per bit of bl - 1 at most
+            bad = true;
+            c = 0;
+        }
+        const uint32_t plen = 1 + vlen(34ull * c);  // 0x12, length
+        const uint32_t sz = on ? plen + 34 * c : 0;
+        const uint32_t ic = wave_incl_scan_u32(c, lane), is = wave_incl_scan_u32(sz, lane);
+        uint8_t *mine = cur + (is - sz);
+        L.pre[lane] = ic - c;
+        if (lane == 63) L.pre[64] = ic;
+        L.base[lane] = (uint64_t)(uintptr_t)(mine + plen);
+        if (on) {  // nested InclusionProof: terms only (leaf and width are zero)
+            g8 *b = (g8 *)mine;
+            uint32_t v = 34 * c;
+            *b++ = 0x12;
+            while (v >= 0x80) {
+                *b++ = (uint8_t)(v | 0x80);
+                v >>= 7;
+            }
+            *b = (uint8_t)v;
+        }
+        __syncthreads();
+        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)ic, 63);
+        uint32_t m = 0;
+        wave_run34(total, lane, [&](uint64_t r, uint8_t *&dst, uint32_t &tag) {
+            while (m + 1 < 64 && L.pre[m + 1] <= r) m++;  // proof of record r (only forward)
+            const uint32_t q = (uint32_t)r - L.pre[m], cm = L.pre[m + 1] - L.pre[m];
+            dst = reinterpret_cast<uint8_t *>(L.base[m]) + 34 * q;
+            tag = 0x1a;
+            return dlog + 32 * L.idx[m * maxc + (cm - 1 - q)];
+        });
+        cur += (uint32_t)__builtin_amdgcn_readlane((int)is, 63);
+    }
+    if (__any(bad) || cur != adv + framed64(pt.adv_body))
+        if (lane == 0) status[p] = MH_ERR_ILLEGAL_STATE;
+}
+
+uint64_t pb_dual_v1_scratch_bytes(uint64_t n) {
+    return ((n * 8 + 255) & ~255ull) + ((n * sizeof(PbDual1Parts) + 255) & ~255ull) +
+           ((pb_scan_temp_bytes(n) + 255) & ~255ull) + 256;
+}
+
+// scratch: sizes[n] (u64) | parts[n] | scan temp
+hipError_t launch_pb_dual_v1(hipStream_t st, Timer *tm, int phase, const uint8_t *dlog,
+                             uint64_t size, uint64_t n, const MhTxHeader *src,
+                             const MhTxHeader *tgt, const uint8_t *md_blob, uint64_t first_tx,
+                             uint64_t count, const uint8_t *alh, const uint8_t *inner, uint8_t *out,
+                             uint64_t out_cap, uint64_t *off, int32_t *status, uint8_t *scratch) {
+    if (!n) return hipMemsetAsync(off, 0, sizeof(uint64_t), st);
+    uint64_t *sizes = reinterpret_cast<uint64_t *>(scratch);
+    PbDual1Parts *parts = reinterpret_cast<PbDual1Parts *>(scratch + ((n * 8 + 255) & ~255ull));
+    uint8_t *temp = reinterpret_cast<uint8_t *>(parts) + ((n * sizeof(PbDual1Parts) + 255) & ~255ull);
+    if (phase & 1) {
+        TimerScope ts(tm, "pb_dual1_size", st);
+        hipLaunchKernelGGL(k_pb_dual1_size, dim3(grid_for(n, 4)), dim3(256), 0, st, size, n, src,
+                           tgt, md_blob, first_tx, count, sizes, parts, status);
+        if (hipError_t e = hipGetLastError()) return e;
+        if (hipError_t e = pb_offsets(st, n, sizes, off, temp)) return e;
+    }
+    if (phase & 2) {
+        TimerScope ts(tm, "pb_dual1_write", st);
+        hipLaunchKernelGGL(k_pb_dual1_write, dim3((unsigned)n), dim3(64), 0, st, dlog, size, n, src,
+                           tgt, md_blob, first_tx, count, alh, inner, off, parts, out, out_cap,
+                           status);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    return hipSuccess;
+}
+
 }  // namespace mh

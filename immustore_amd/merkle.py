@@ -436,6 +436,25 @@ class AHtree:
             self.handle, s.size, _addr(s), _addr(t), _addr(bp), bl, _addr(out), cap, _addr(off),
             _addr(st)), s.size)
 
+    def dual_proof_pb_batch(self, src_hdrs, tgt_hdrs, md_blob, first_tx: int, alh, inner):
+        """ImmuStore.DualProof (v1, immustore.go:2394-2562: with its LinearProof
+        and LinearAdvanceProof) for many header pairs, each encoded on the
+        device as the DualProof protobuf message (schema.proto:388) ->
+        (messages, status[n]).  alh / inner: Alh and innerHash of the txs
+        first_tx .. first_tx + len(alh) - 1 (tx_alh_batch's outputs), the
+        digest window the linear parts are gathered from."""
+        from .txlayer import _blob, _hdrs
+        s, t = _hdrs(src_hdrs), _hdrs(tgt_hdrs)
+        bp, bl = _blob(md_blob)
+        a, i = _digests(alh), _digests(inner)
+        count = a.shape[0]
+        if i.shape[0] != count:
+            raise N.ErrIllegalArguments(N.MH_ERR_ILLEGAL_ARGUMENTS, "alh / inner lengths differ")
+        return _pb_call(lambda out, cap, off, st: self._lib.mh_ahtree_dual_proof_pb_batch(
+            self.handle, s.size, _addr(s), _addr(t), _addr(bp), bl, first_tx, count,
+            _addr(a) if count else None, _addr(i) if count else None, _addr(out), cap, _addr(off),
+            _addr(st)), s.size)
+
     def reset_size(self, new_size: int):
         N.check(self._lib.mh_ahtree_reset_size(self.handle, new_size))
 

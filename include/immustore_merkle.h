@@ -74,6 +74,10 @@ extern "C" {
                                            hash-value check (pkg/verification/verification.go:60-76),
                                            i.e. raised BEFORE the document decode (:78-110) */
 #define MH_ERR_COLLECTIVE 23            /* RCCL unavailable or a collective failed (mh_multi_*) */
+#define MH_ERR_CORRUPTED_TX_DATA 24     /* store.ErrCorruptedTxData immustore.go:71 (binary linking
+                                         * mismatch, immustore.go:2416) */
+#define MH_ERR_TX_NOT_FOUND 25          /* store.ErrTxNotFound immustore.go:85 (a tx outside the
+                                         * digest window of mh_*_dual_proof_pb_batch) */
 
 #define MH_MAX_TX_METADATA_LEN 268 /* maxTxMetadataLen tx_metadata.go:36-39 */
 #define MH_MAX_KV_METADATA_LEN 11  /* maxKVMetadataLen kv_metadata.go:41-43 */
@@ -963,6 +967,54 @@ int mh_dev_dual_proof_v2_pb_batch(mh_ctx *ctx, int phase, const uint8_t *dlog, u
                                   uint64_t n, const mh_tx_header *src, const mh_tx_header *tgt,
                                   const uint8_t *md_blob, uint8_t *out, uint64_t out_cap,
                                   uint64_t *off, int32_t *status, void *scratch);
+
+/* DualProof (v1) messages (schema.proto:388-434; DualProofToProto,
+ * LinearProofToProto, LinearAdvanceProofToProto database_protoconv.go:131-211)
+ * of ImmuStore.DualProof(src[p], tgt[p]) with its LinearProof and
+ * LinearAdvanceProof (immustore.go:2394-2562): the answer of VerifiableGet,
+ * VerifiableSet, VerifiableTxById and the SQL / sorted-set variants
+ * (pkg/database/database.go:805,881).  Replaces the per-proof Go walk over
+ * the tree and the tx log plus the marshalling; same contract as
+ * mh_ahtree_dual_proof_v2_pb_batch (block comment above).
+ * The ahtree parts -- InclusionProof(src.ID, tgt.BlTxID), ConsistencyProof(
+ * src.BlTxID, tgt.BlTxID), InclusionProof(tgt.BlTxID, tgt.BlTxID) and the
+ * LinearAdvanceProof's InclusionProof(k, tgt.BlTxID) (ahtree.go:525-597) --
+ * are taken from t's dLog.  The linear parts are Alh / innerHash values of
+ * whole txs, which the dLog does not hold (a leaf is SHA-256(0x00 || Alh)):
+ * the caller passes a digest window, alh[32 k] and inner[32 k] of tx
+ * first_tx + k for k < count, exactly the alh_out / inner_out of
+ * mh_tx_alh_batch over those headers.  Nothing is hashed; the call gathers and
+ * encodes.  A tx the proof needs outside the window is Go's ErrTxNotFound.
+ * status[p], first match in Go's order: MH_ERR_ILLEGAL_ARGUMENTS (src.ID == 0:
+ * the store holds no tx 0 and Go would walk the tree from leaf 0 -- a
+ * deliberate narrowing, as for DualProofV2), MH_ERR_SOURCE_TX_NEWER (src.ID >
+ * tgt.ID; or from LinearProof / LinearAdvanceProof, :2473, :2515),
+ * MH_ERR_UNEXISTENT_DATA (tgt.BlTxID beyond the tree), MH_ERR_CORRUPTED_TX_DATA
+ * (src.BlTxID > tgt.BlTxID, :2416), MH_ERR_TX_NOT_FOUND, MH_ERR_CORRUPTED_DATA
+ * (metadata bytes).  Lengths are 64-bit: the linear parts have no cap but
+ * out_cap.  TargetBlTxAlh is always written (32 zero bytes when tgt.BlTxID ==
+ * 0: the Go field is a slice of an array); a nil LinearAdvanceProof is omitted;
+ * nested InclusionProofs carry terms only. */
+int mh_ahtree_dual_proof_pb_batch(mh_ahtree *t, uint64_t n, const mh_tx_header *src,
+                                  const mh_tx_header *tgt, const uint8_t *md_blob,
+                                  uint64_t md_blob_len, uint64_t first_tx, uint64_t count,
+                                  const uint8_t *alh, const uint8_t *inner, uint8_t *out,
+                                  uint64_t out_cap, uint64_t *off, int32_t *status);
+/* Device variant of ImmuStore.DualProof + DualProofToProto (all pointers
+ * device memory, asynchronous, no allocation; phase as above): dlog holds the
+ * tree of `size` leaves, alh / inner (16-byte aligned) are the digest window
+ * as mh_dev_tx_alh_batch writes it, scratch = mh_pb_dual_scratch_size(n)
+ * bytes.  n < 2^31.  Phase 1 leaves the per-message part counts and
+ * sub-message lengths in scratch: a phase-2 call needs that same scratch,
+ * untouched, with the same off and status (else MH_ERR_ILLEGAL_STATE at
+ * best).  A message that phase 2 marked MH_ERR_BUFFER_TOO_SMALL keeps that
+ * status until phase 1 runs again. */
+uint64_t mh_pb_dual_scratch_size(uint64_t n);
+int mh_dev_dual_proof_pb_batch(mh_ctx *ctx, int phase, const uint8_t *dlog, uint64_t size,
+                               uint64_t n, const mh_tx_header *src, const mh_tx_header *tgt,
+                               const uint8_t *md_blob, uint64_t first_tx, uint64_t count,
+                               const uint8_t *alh, const uint8_t *inner, uint8_t *out,
+                               uint64_t out_cap, uint64_t *off, int32_t *status, void *scratch);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
