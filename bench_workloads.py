@@ -51,6 +51,14 @@
                     resident Alh / innerHash window (mh_dev_dual_proof_pb_batch:
                     sizes pass, scan, write pass); proofs/s and output GiB/s; a
                     sample checked against the CPU restatement of the tests.
+  --workload dualv1verify  the client's side of that wire: about 1 GiB of DualProof
+                    (v1) messages (device-generated over the tests' synthetic store of
+                    3000 txs, so every proof really verifies) in pinned host memory,
+                    verified (a) by mh_dual_proof_pb_decode_batch then
+                    mh_verify_dual_proof_batch with pinned host arrays and (b) by the
+                    fused mh_verify_dual_proof_pb_batch, timed in the same run, next to
+                    the pinned H2D time of the message bytes; a sample of verdicts
+                    checked against the oracle.
 
 Each prints one JSON line.  bench.py stays the driver's headline benchmark.
 
@@ -415,7 +423,7 @@ def distributed_main(a):
 def make_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--workload", choices=["c3", "c5", "c2e2e", "txlog", "commit", "wire", "ragged", "document",
-                                          "values", "c3range", "dualv1"],
+                                          "values", "c3range", "dualv1", "dualv1verify"],
                    required=True)
     p.add_argument("--logs", action="store_true",
                    help="c3: also write the pLog / cLog appendable records (8(f) row 4)")
@@ -438,7 +446,9 @@ def make_parser():
     p.add_argument("--no-check", action="store_true", help="ragged: skip the oracle check")
     p.add_argument("--docs", type=int, default=8192, help="document: documents")
     p.add_argument("--doc-entries", type=int, default=64, help="document: entries per tx")
-    p.add_argument("--v1-proofs", type=int, default=10 ** 5, help="dualv1: header pairs")
+    p.add_argument("--v1-proofs", type=int, default=None,
+                   help="dualv1: header pairs (default 10^5); dualv1verify: random pairs "
+                        "(default: as many as make about 1 GiB of messages)")
     p.add_argument("--v1-depth", type=int, default=20, help="dualv1: log2 of the appends")
     return p
 
@@ -1543,7 +1553,7 @@ def run_single(a):
 
     elif a.workload == "dualv1":
         from immustore_amd.txlayer import TX_HEADER
-        P, W = a.v1_proofs, 1 << a.v1_depth
+        P, W = a.v1_proofs or 10 ** 5, 1 << a.v1_depth
         rng = np.random.default_rng(21)
         # the resident state of a server: the dLog of W appends and the Alh /
         # innerHash of every tx (random digests: the generator hashes nothing)
@@ -1623,6 +1633,176 @@ def run_single(a):
                                  "max": int(sizes.max())},
                "kernel_ms": {k: round(v, 3) for k, v in kd.items()},
                "sample_vs_restatement": bool(ok)}
+
+    elif a.workload == "dualv1verify":
+        import ctypes as C
+        from immustore_amd import txlayer as TL
+        sys.path.insert(0, os.path.join(HERE, "oracle"))
+        sys.path.insert(0, os.path.join(HERE, "tests"))
+        import oracle as O
+        import wire as WIRE
+        import dual_v1_gen_util as U
+        from dual_v1_verify_util import reference
+        s = U.synthetic_store()
+        W = U.N_TX
+        rng = np.random.default_rng(23)
+        A = lambda x: x.ctypes.data  # noqa: E731
+        todev = lambda x: torch.from_numpy(np.array(x).view(np.uint8).reshape(-1)).to(dev)  # noqa: E731
+        alh_h = np.stack([np.frombuffer(x, np.uint8) for x in s.alhs])
+        alh = todev(alh_h)
+        inner = todev(np.stack([np.frombuffer(x, np.uint8) for x in s.inners]))
+        blob = todev(np.frombuffer(s.blob + bytes(16), np.uint8))
+        dlog = torch.empty(m.nodes_upto(W) * 32, dtype=torch.uint8, device=dev)
+        N.check(L.mh_dev_ahtree_append_batch(ctx.handle, dlog.data_ptr(), 0, alh.data_ptr(), W, 32,
+                                             None))
+
+        def generate(P):
+            """P random pairs -> (messages, offsets, source ids, target ids), on the host"""
+            tid = rng.integers(1, W + 1, P)
+            sid = np.minimum((rng.random(P) * tid).astype(np.int64) + 1, tid)
+            hs, ht = todev(s.recs[sid - 1]), todev(s.recs[tid - 1])
+            off = torch.empty(P + 1, dtype=torch.int64, device=dev)
+            st = torch.empty(P, dtype=torch.int32, device=dev)
+            scratch = torch.empty(L.mh_pb_dual_scratch_size(P), dtype=torch.uint8, device=dev)
+            outb = None
+            for phase in (1, 3):
+                N.check(L.mh_dev_dual_proof_pb_batch(
+                    ctx.handle, phase, dlog.data_ptr(), W, P, hs.data_ptr(), ht.data_ptr(),
+                    blob.data_ptr(), 1, W, alh.data_ptr(), inner.data_ptr(),
+                    outb.data_ptr() if outb is not None else None,
+                    outb.numel() if outb is not None else 0, off.data_ptr(), st.data_ptr(),
+                    scratch.data_ptr()))
+                sync()
+                if phase == 1:
+                    outb = torch.empty(int(off[P].item()), dtype=torch.uint8, device=dev)
+            assert int(st.abs().sum().item()) == 0
+            return outb.cpu().numpy(), off.cpu().numpy().astype(np.uint64), sid, tid
+
+        P = a.v1_proofs
+        if P is None:  # about 1 GiB of messages, from the mean of a sample
+            _, o_, _, _ = generate(2048)
+            P = int((1 << 30) / (int(o_[-1]) / 2048))
+        msgs_h, moff, sid, tid = generate(P)
+        total = int(moff[-1])
+        sizes = np.diff(moff)
+
+        def pin(shape, dtype):
+            n_ = int(np.prod(shape)) * np.dtype(dtype).itemsize
+            t_ = torch.empty(max(n_, 1), dtype=torch.uint8).pin_memory()
+            keep.append(t_)
+            return t_.numpy()[:n_].view(dtype).reshape(shape)
+
+        keep = []
+        msgs = pin(total + 16, np.uint8)
+        msgs[:total] = msgs_h
+        vsrc, vtgt = pin(P, np.uint64), pin(P, np.uint64)
+        vsrc[:], vtgt[:] = sid, tid
+        sa, ta = pin((P, 32), np.uint8), pin((P, 32), np.uint8)
+        sa[:], ta[:] = alh_h[sid - 1], alh_h[tid - 1]
+        # (a) the two existing calls, every array pinned: sizes from a first call
+        d = {"src_hdr": pin(P, TL.TX_HEADER), "tgt_hdr": pin(P, TL.TX_HEADER),
+             "md_blob": pin(2 * P * 268, np.uint8), "target_bl_tx_alh": pin((P, 32), np.uint8),
+             "has_linear": pin(P, np.uint8), "linear_src": pin(P, np.uint64),
+             "linear_tgt": pin(P, np.uint64), "has_advance": pin(P, np.uint8),
+             "advance_incl_first": pin(P + 1, np.uint64), "advance_incl_off": pin(1, np.uint64)}
+        lists = ("incl", "cons", "last", "linear", "advance")
+        for t_ in lists:
+            d[t_ + "_off"] = pin(P + 1, np.uint64)
+        dst = pin(P, np.int32)
+        caps = {}
+
+        def decoded():
+            for t_ in lists + ("advance_incl",):
+                d[t_ + "_terms"] = pin((max(caps.get(t_, 0), 1), 32), np.uint8)
+            d["advance_incl_off"] = pin(caps.get("nested", 0) + 1, np.uint64)
+            return TL._DualProofDecoded(*[A(d[f]) for f, _ in TL._DualProofDecoded._fields_[:21]],
+                                        *[caps.get(t_, 0) for t_ in lists], caps.get("nested", 0),
+                                        caps.get("advance_incl", 0), 0, 0)
+
+        dd = decoded()
+        rc = L.mh_dual_proof_pb_decode_batch(ctx.handle, P, A(msgs), A(moff), C.byref(dd), A(dst))
+        assert rc == N.MH_ERR_BUFFER_TOO_SMALL, rc
+        caps = {t_: int(d[t_ + "_off"][P]) for t_ in lists}
+        caps["nested"], caps["advance_incl"] = int(dd.nested_proofs), int(dd.nested_terms)
+        dd = decoded()
+        oka, okb, stb = pin(P, np.uint8), pin(P, np.uint8), pin(P, np.int32)
+        B = TL._DualProofBatch(
+            P, A(d["src_hdr"]), A(d["tgt_hdr"]), A(d["md_blob"]), d["md_blob"].size,
+            A(d["incl_off"]), A(d["incl_terms"]), A(d["cons_off"]), A(d["cons_terms"]),
+            A(d["target_bl_tx_alh"]), A(d["last_off"]), A(d["last_terms"]), A(d["has_linear"]),
+            A(d["linear_src"]), A(d["linear_tgt"]), A(d["linear_off"]), A(d["linear_terms"]),
+            A(d["has_advance"]), A(d["advance_off"]), A(d["advance_terms"]),
+            A(d["advance_incl_first"]), A(d["advance_incl_off"]), A(d["advance_incl_terms"]),
+            A(vsrc), A(vtgt), A(sa), A(ta))
+
+        def step_decode():
+            N.check(L.mh_dual_proof_pb_decode_batch(ctx.handle, P, A(msgs), A(moff), C.byref(dd),
+                                                    A(dst)))
+
+        def step_verify():
+            N.check(L.mh_verify_dual_proof_batch(ctx.handle, C.byref(B), A(oka)))
+
+        def step_two_calls():
+            step_decode()
+            step_verify()
+
+        def step_fused():
+            N.check(L.mh_verify_dual_proof_pb_batch(ctx.handle, P, A(msgs), A(moff), A(vsrc),
+                                                    A(vtgt), A(sa), A(ta), A(stb), A(okb)))
+
+        # the floor of either path: the message bytes over the link, pinned
+        landing = torch.empty(total, dtype=torch.uint8, device=dev)
+        src_pin = torch.from_numpy(msgs[:total])
+
+        def step_h2d():
+            landing.copy_(src_pin, non_blocking=True)
+
+        prewarm(step_fused, sync, a.prewarm)
+        th2d = timed(step_h2d, a.steps, a.warmup, sync)
+        ta1 = timed(step_two_calls, a.steps, a.warmup, sync)
+        tdec = timed(step_decode, a.steps, 0, sync)
+        tfus = timed_k(ctx, step_fused, a.steps, a.warmup, sync)
+        kd = {k: round(ctx.timing(k)[0] / (a.steps + a.warmup), 3)
+              for k in ("pbd_dual1_size", "pbd_dual1_write", "dp1_prep", "tx_alh", "leaf_for",
+                        "ahtree_verify", "linear_verify", "advance_chain", "dp1_nested",
+                        "dp1_verdict")}
+        ta2 = timed(step_two_calls, a.steps, a.warmup, sync)
+        # the fused call with every 128 MiB chunk decoded alone (no groups of chunks)
+        os.environ["MH_PB_GROUP_RATIO"] = "0"
+        tfus0 = timed(step_fused, max(1, a.steps // 2), 1, sync)
+        del os.environ["MH_PB_GROUP_RATIO"]
+        ok = bool((dst == 0).all() and (stb == 0).all() and oka.all() and okb.all())
+        for k in [int(x) for x in rng.integers(0, P, 100)]:
+            raw = msgs_h[int(moff[k]):int(moff[k + 1])].tobytes()
+            ok &= reference(WIRE, O, raw, int(sid[k]), int(tid[k]), bytes(sa[k]), bytes(ta[k])) == \
+                (int(stb[k]), bool(okb[k])) == (0, True)
+        # ... and a sample that must fail: the target id one too high
+        vtgt[:] = tid + 1
+        step_fused()
+        sync()
+        ok &= bool((stb == 0).all()) and not okb[sid != tid].any()
+        vtgt[:] = tid
+        ta_ = min(ta1, ta2)
+        out = {"metric": "DualProof (v1) messages verified from the wire, %d x (synthetic store of "
+                         "%d txs, not a 2^20 tree; every proof verifies)" % (P, W),
+               "value": round(P / tfus / 1e3, 1), "unit": "k proofs/s (fused call)",
+               "ms_per_step": round(tfus * 1e3, 3), "message_bytes": total,
+               "message_bytes_each": {"min": int(sizes.min()), "mean": round(float(sizes.mean()), 1),
+                                      "max": int(sizes.max())},
+               "in_GBps": round(total / tfus / 1e9, 2),
+               "two_calls_pinned": {"k_proofs_per_s": round(P / ta_ / 1e3, 1),
+                                    "ms_per_step": [round(ta1 * 1e3, 3), round(ta2 * 1e3, 3)],
+                                    "spread_ms": round(abs(ta1 - ta2) * 1e3, 3),
+                                    "decode_ms": round(tdec * 1e3, 3),
+                                    "note": "mh_dual_proof_pb_decode_batch + "
+                                            "mh_verify_dual_proof_batch, every array pinned; run "
+                                            "before and after the fused call"},
+               "fused_vs_two_calls": round(ta_ / tfus, 2),
+               "fused_chunk_by_chunk_ms": round(tfus0 * 1e3, 3),
+               "h2d_floor": {"ms": round(th2d * 1e3, 3), "pinned_GBps": round(total / th2d / 1e9, 2),
+                             "fused_over_floor": round(tfus / th2d, 2)},
+               "kernel_ms": kd,
+               "sample_vs_oracle": bool(ok)}
 
     out["workload"] = a.workload
     ctx.close()

@@ -139,3 +139,88 @@ func (pt *ProofTree) DualProofBatch(src, tgt []*TxHeader, firstTx uint64,
 	}
 	return msgs, errs, nil
 }
+
+// packDualProofMessages lays the messages of a batch end to end, as the C
+// calls read them (message p = buf[off[p]:off[p+1]]).
+func packDualProofMessages(msgs [][]byte) (buf []byte, off []uint64) {
+	off = make([]uint64, len(msgs)+1)
+	total := 0
+	for _, m := range msgs {
+		total += len(m)
+	}
+	buf = make([]byte, 0, total+1)
+	for p, m := range msgs {
+		buf = append(buf, m...)
+		off[p+1] = uint64(len(buf))
+	}
+	return append(buf, 0), off
+}
+
+// VerifyDualProofMessages is what pkg/client does with every VerifiableGet /
+// VerifiableSet / VerifiableTxById answer (client.go:1090-1117, 1150-1213) --
+// proto.Unmarshal, schema.DualProofFromProto, store.VerifyDualProof
+// (verification.go:127-235) -- for a batch of marshalled schema.DualProof
+// messages in one device pass: the messages go up once, one verdict each comes
+// back.  ok[p] is VerifyDualProof(proof p, src[p], tgt[p], srcAlh[p],
+// tgtAlh[p]); a message that does not decode (ErrCorruptedData at
+// client.go:1112-1114) or lacks a header or its linear proof is false.  A
+// message without LinearAdvanceProof is verified as it stands: nothing is
+// fetched, FillMissingLinearAdvanceProof stays with the caller.
+func VerifyDualProofMessages(msgs [][]byte, src, tgt []uint64,
+	srcAlh, tgtAlh [][sha256.Size]byte) (ok []bool, err error) {
+	return verifyDualProofMessages(msgs, src, tgt, srcAlh, tgtAlh, false)
+}
+
+// VerifyDualProofMessagesClique is VerifyDualProofMessages over every GPU of
+// the process: the batch cut into parts of nearly equal message bytes, one
+// per device over its own link (mh_multi_verify_dual_proof_pb_batch), on a
+// clique checked out of the process's pool.
+func VerifyDualProofMessagesClique(msgs [][]byte, src, tgt []uint64,
+	srcAlh, tgtAlh [][sha256.Size]byte) (ok []bool, err error) {
+	return verifyDualProofMessages(msgs, src, tgt, srcAlh, tgtAlh, true)
+}
+
+func verifyDualProofMessages(msgs [][]byte, src, tgt []uint64,
+	srcAlh, tgtAlh [][sha256.Size]byte, clique bool) ([]bool, error) {
+	n := len(msgs)
+	if len(src) != n || len(tgt) != n || len(srcAlh) != n || len(tgtAlh) != n {
+		return nil, ErrIllegalArguments
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	buf, off := packDualProofMessages(msgs)
+	status := make([]int32, n)
+	verdict := make([]uint8, n)
+	var st C.int
+	if clique {
+		m, e := mi355x.AcquireClique()
+		if e != nil {
+			return nil, e
+		}
+		st = C.mh_multi_verify_dual_proof_pb_batch((*C.mh_multi)(m), C.uint64_t(n),
+			(*C.uint8_t)(unsafe.Pointer(&buf[0])), (*C.uint64_t)(unsafe.Pointer(&off[0])),
+			(*C.uint64_t)(unsafe.Pointer(&src[0])), (*C.uint64_t)(unsafe.Pointer(&tgt[0])),
+			(*C.uint8_t)(unsafe.Pointer(&srcAlh[0][0])), (*C.uint8_t)(unsafe.Pointer(&tgtAlh[0][0])),
+			(*C.int32_t)(unsafe.Pointer(&status[0])), (*C.uint8_t)(unsafe.Pointer(&verdict[0])))
+		mi355x.ReleaseClique(m, int(st))
+	} else {
+		p, e := mi355x.Context()
+		if e != nil {
+			return nil, e
+		}
+		st = C.mh_verify_dual_proof_pb_batch((*C.mh_ctx)(p), C.uint64_t(n),
+			(*C.uint8_t)(unsafe.Pointer(&buf[0])), (*C.uint64_t)(unsafe.Pointer(&off[0])),
+			(*C.uint64_t)(unsafe.Pointer(&src[0])), (*C.uint64_t)(unsafe.Pointer(&tgt[0])),
+			(*C.uint8_t)(unsafe.Pointer(&srcAlh[0][0])), (*C.uint8_t)(unsafe.Pointer(&tgtAlh[0][0])),
+			(*C.int32_t)(unsafe.Pointer(&status[0])), (*C.uint8_t)(unsafe.Pointer(&verdict[0])))
+	}
+	if st != C.MH_OK {
+		return nil, mapErr(st)
+	}
+	ok := make([]bool, n)
+	for p := range ok {
+		ok[p] = status[p] == 0 && verdict[p] != 0
+	}
+	return ok, nil
+}

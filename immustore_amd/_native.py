@@ -287,6 +287,7 @@ SIGNATURES = {
     "mh_verify_dual_proof_batch": (i32, [vp, vp, u8p]),
     "mh_dual_proof_pb_decode_batch": (i32, [vp, u64, u8p, vp, vp, vp]),
     "mh_verify_dual_proof_v2_pb_batch": (i32, [vp, u64, u8p, vp, vp, vp, u8p, u8p, vp]),
+    "mh_verify_dual_proof_pb_batch": (i32, [vp, u64, u8p, vp, vp, vp, u8p, u8p, vp, u8p]),
     "mh_verify_document_batch": (i32, [vp, vp, vp, u8p]),
     "mh_commit_queue_new": (i32, [vp, i32, u64, u32, u32, C.POINTER(vp)]),
     "mh_commit_queue_free": (i32, [vp]),
@@ -320,6 +321,7 @@ SIGNATURES = {
     "mh_multi_verify_values_batch": (i32, [vp, u64, u8p, vp, vp, u8p, vp, C.POINTER(u64)]),
     "mh_multi_verify_document_batch": (i32, [vp, vp, vp, u8p]),
     "mh_multi_verify_dual_proof_v2_pb_batch": (i32, [vp, u64, u8p, vp, vp, vp, u8p, u8p, vp]),
+    "mh_multi_verify_dual_proof_pb_batch": (i32, [vp, u64, u8p, vp, vp, vp, u8p, u8p, vp, u8p]),
     "mh_multi_precommit_batch": (i32, [vp, i32, u64, u64, vp, u8p, vp, u8p, vp, u8p, vp, u8p,
                                        u8p, u8p, u8p, u8p, vp]),
     "mh_dev_ahtree_range_local": (i32, [vp, u64, u8p, u64, i32, i32, u8p, u32, u8p, u8p, u8p]),

@@ -1155,6 +1155,35 @@ extern "C" int mh_multi_verify_dual_proof_v2_pb_batch(mh_multi *m, uint64_t n, c
     });
 }
 
+// The fused DualProof (v1) wire verify (DualProofFromProto,
+// database_protoconv.go:213-224, + VerifyDualProof, verification.go:127-235)
+// over n messages, split into K parts of nearly equal message bytes.
+extern "C" int mh_multi_verify_dual_proof_pb_batch(mh_multi *m, uint64_t n, const uint8_t *msgs,
+                                                   const uint64_t *msg_off, const uint64_t *src,
+                                                   const uint64_t *tgt, const uint8_t *src_alh,
+                                                   const uint8_t *tgt_alh, int32_t *status,
+                                                   uint8_t *ok) {
+    return mh_guard([&]() -> int {
+        if (!m) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (m->K == 1 || n < (uint64_t)m->K)
+            return mh_verify_dual_proof_pb_batch(m->ctx[0], n, msgs, msg_off, src, tgt, src_alh,
+                                                 tgt_alh, status, ok);
+        if (!msg_off || !src || !tgt || !src_alh || !tgt_alh || !status || !ok)
+            return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (!monotonic(msg_off, n)) return MH_ERR_ILLEGAL_ARGUMENTS;
+        const std::vector<uint64_t> t =
+            split_by_bytes(n, m->K, [&](uint64_t i) { return msg_off[i]; });
+        std::lock_guard<std::mutex> lk(m->mu);
+        return per_device(m->K, [&](int d) -> int {
+            const uint64_t lo = t[d], hi = t[d + 1];
+            if (hi == lo) return MH_OK;
+            return mh_verify_dual_proof_pb_batch(m->ctx[d], hi - lo, msgs, msg_off + lo, src + lo,
+                                                 tgt + lo, src_alh + 32 * lo, tgt_alh + 32 * lo,
+                                                 status + lo, ok + lo);
+        });
+    });
+}
+
 // precommit's hashing (immustore.go:1620-1632, 2301-2313 -> tx.go:332-355) for
 // a batch of transactions, split into K parts of whole transactions with
 // nearly equal value bytes; part d runs on device d's own commit pipe (made

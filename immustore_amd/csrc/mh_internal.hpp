@@ -231,6 +231,14 @@ hipError_t launch_advance_chain(hipStream_t st, Timer *tm, uint64_t n, const uin
                                 const uint64_t *cnt, const uint64_t *term_off,
                                 const uint8_t *terms, const uint64_t *first,
                                 const uint8_t *end_alh, uint8_t *leaves_src, uint8_t *ok);
+// the same chain over every proof of a batch, uncompacted: lane p runs only
+// when state[p] == 0 (its lengths checked by whoever set the state) and
+// otherwise reads no term and writes ok[p] = 0
+hipError_t launch_advance_chain_gated(hipStream_t st, Timer *tm, uint64_t n, const uint8_t *state,
+                                      const uint64_t *start, const uint64_t *cnt,
+                                      const uint64_t *term_off, const uint8_t *terms,
+                                      const uint64_t *first, const uint8_t *end_alh,
+                                      uint8_t *leaves_src, uint8_t *ok);
 // roots of many htrees (widths leaf_off[t+1]-leaf_off[t], small), one lane
 // each, in place over nodes = their leaf hashes back to back
 constexpr uint64_t kSmallTreeMax = 64;

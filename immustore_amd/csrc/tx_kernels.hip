@@ -207,6 +207,39 @@ __global__ __launch_bounds__(256) void k_advance_chain(
     ok[p] = d == 0;
 }
 
+// The same chain for every proof of a batch, none compacted away (the fused
+// wire verify keeps the three-way state of verification.go:90-104 on the
+// device): lane p runs the chain only when state[p] == 0, which promises
+// cnt[p] + 1 terms from term_off[p] and cnt[p] nested proofs from first[p];
+// any other lane touches no term and no leaf.
+__global__ __launch_bounds__(256) void k_advance_chain_gated(
+    uint64_t n, const uint8_t *__restrict__ state, const uint64_t *__restrict__ start,
+    const uint64_t *__restrict__ cnt, const uint64_t *__restrict__ term_off,
+    const uint8_t *__restrict__ terms, const uint64_t *__restrict__ first,
+    const uint8_t *__restrict__ end_alh, uint8_t *__restrict__ leaves_src,
+    uint8_t *__restrict__ ok) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    if (state[p] != 0) {
+        ok[p] = 0;
+        return;
+    }
+    const uint64_t t0 = term_off[p], c0 = cnt[p], s = start[p], f = first[p];
+    uint32_t c[8], x[8];
+    load_digest(terms + t0 * 32, c);
+    for (uint64_t k = 0; k < c0; k++) {
+        store_digest(leaves_src + (f + k) * 32, c);
+        uint32_t term[8];
+        load_digest(terms + (t0 + k + 1) * 32, term);
+        alh_hash(s + 2 + k, c, term, c);
+    }
+    load_digest(end_alh + p * 32, x);
+    uint32_t d = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) d |= c[j] ^ x[j];
+    ok[p] = d == 0;
+}
+
 // Entry digest (tx.go:690-731) -- and, with leaf != 0, its htree leaf
 // SHA256(0x00 || digest) (htree.go:79-83) -- hashed in place from the raw
 // tx-log entry record (sha256_skip12): no message buffer, no offsets scan.
@@ -780,6 +813,18 @@ hipError_t launch_advance_chain(hipStream_t st, Timer *tm, uint64_t n, const uin
     TimerScope ts(tm, "advance_chain", st);
     hipLaunchKernelGGL(k_advance_chain, dim3(grid_for(n, 256)), dim3(256), 0, st, n, start, cnt,
                        term_off, terms, first, end_alh, leaves_src, ok);
+    return hipGetLastError();
+}
+
+hipError_t launch_advance_chain_gated(hipStream_t st, Timer *tm, uint64_t n, const uint8_t *state,
+                                      const uint64_t *start, const uint64_t *cnt,
+                                      const uint64_t *term_off, const uint8_t *terms,
+                                      const uint64_t *first, const uint8_t *end_alh,
+                                      uint8_t *leaves_src, uint8_t *ok) {
+    if (!n) return hipSuccess;
+    TimerScope ts(tm, "advance_chain", st);
+    hipLaunchKernelGGL(k_advance_chain_gated, dim3(grid_for(n, 256)), dim3(256), 0, st, n, state,
+                       start, cnt, term_off, terms, first, end_alh, leaves_src, ok);
     return hipGetLastError();
 }
 

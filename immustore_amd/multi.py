@@ -221,6 +221,24 @@ class MultiDevice:
             _addr(st)))
         return st
 
+    def verify_dual_proof_pb_batch(self, msgs, src, tgt, src_alh, tgt_alh):
+        """txlayer.verify_dual_proof_pb_batch (DualProof v1) over the devices
+        (parts of nearly equal message bytes) -> (status[n], ok[n])."""
+        from .txlayer import _d32
+        n = len(msgs)
+        if n == 0:
+            return np.zeros(0, np.int32), np.zeros(0, bool)
+        off = np.zeros(n + 1, np.uint64)
+        off[1:] = np.cumsum([len(x) for x in msgs], dtype=np.uint64)
+        buf = np.frombuffer(b"".join(msgs) + b"\0", np.uint8)
+        s_, t_ = np.asarray(src, np.uint64), np.asarray(tgt, np.uint64)
+        sa, ta = _d32(src_alh, n), _d32(tgt_alh, n)
+        st, ok = np.zeros(n, np.int32), np.zeros(n, np.uint8)
+        N.check(N.load().mh_multi_verify_dual_proof_pb_batch(
+            self.handle, n, _addr(buf), _addr(off), _addr(s_), _addr(t_), _addr(sa), _addr(ta),
+            _addr(st), _addr(ok)))
+        return st, ok.astype(bool)
+
     def verify_document_batch(self, docs):
         """txlayer.verify_document_batch over the devices
         (mh_multi_verify_document_batch) -> (status[n], target_alh[n, 32])."""

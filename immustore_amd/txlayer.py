@@ -592,3 +592,23 @@ def verify_dual_proof_v2_pb_batch(msgs, src, tgt, src_alh, tgt_alh,
                                                       _addr(s_), _addr(t_), _addr(sa), _addr(ta),
                                                       _addr(st)))
     return st
+
+
+def verify_dual_proof_pb_batch(msgs, src, tgt, src_alh, tgt_alh, ctx: Optional[Context] = None):
+    """DualProofFromProto + VerifyDualProof (v1) over many encoded DualProof
+    messages in one device pass (mh_verify_dual_proof_pb_batch) ->
+    (status[n] int32: the decode status, ok[n] bool: status 0 and the proof
+    verifies).  A message without LinearAdvanceProof is verified as it stands."""
+    n = len(msgs)
+    if n == 0:
+        return np.zeros(0, np.int32), np.zeros(0, bool)
+    off = np.zeros(n + 1, np.uint64)
+    off[1:] = np.cumsum([len(x) for x in msgs], dtype=np.uint64)
+    buf = np.frombuffer(b"".join(msgs) + b"\0", np.uint8)
+    s_, t_ = np.asarray(src, np.uint64), np.asarray(tgt, np.uint64)
+    sa, ta = _d32(src_alh, n), _d32(tgt_alh, n)
+    st, ok = np.zeros(n, np.int32), np.zeros(n, np.uint8)
+    N.check(N.load().mh_verify_dual_proof_pb_batch(_ctx(ctx).handle, n, _addr(buf), _addr(off),
+                                                   _addr(s_), _addr(t_), _addr(sa), _addr(ta),
+                                                   _addr(st), _addr(ok)))
+    return st, ok.astype(bool)

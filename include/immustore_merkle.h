@@ -862,6 +862,13 @@ int mh_multi_verify_dual_proof_v2_pb_batch(mh_multi *m, uint64_t n, const uint8_
                                            const uint64_t *msg_off, const uint64_t *src,
                                            const uint64_t *tgt, const uint8_t *src_alh,
                                            const uint8_t *tgt_alh, int32_t *status);
+/* The fused DualProof (v1) wire verify over the devices, split by message
+ * bytes like the V2 form; arguments and outputs as
+ * mh_verify_dual_proof_pb_batch (context 0 alone when K == 1 or n < K). */
+int mh_multi_verify_dual_proof_pb_batch(mh_multi *m, uint64_t n, const uint8_t *msgs,
+                                        const uint64_t *msg_off, const uint64_t *src,
+                                        const uint64_t *tgt, const uint8_t *src_alh,
+                                        const uint8_t *tgt_alh, int32_t *status, uint8_t *ok);
 /* VerifyDocument's hashing part (verification.go:37-196) over the devices:
  * parts of nearly equal entries + document bytes, as mh_verify_document_batch. */
 int mh_multi_verify_document_batch(mh_multi *m, const mh_document_batch *batch, int32_t *status,
@@ -928,6 +935,31 @@ int mh_verify_dual_proof_v2_pb_batch(mh_ctx *ctx, uint64_t n, const uint8_t *msg
                                      const uint64_t *msg_off, const uint64_t *src,
                                      const uint64_t *tgt, const uint8_t *src_alh,
                                      const uint8_t *tgt_alh, int32_t *status);
+/* The same for DualProof (v1), the proof VerifiableGet / VerifiableSet /
+ * VerifiableTxById answer with: DualProofFromProto then store.VerifyDualProof
+ * (verification.go:127-235) for n messages in one device pass -- message p =
+ * msgs[msg_off[p] .. msg_off[p+1]) (host memory, pageable or pinned; msg_off[0]
+ * need not be 0) goes up once, in chunks of MH_PB_CHUNK_MIB MiB (default 128,
+ * the variable the V2 call reads), and only n statuses and n verdict bytes
+ * come back.  Consecutive chunks are decoded and verified together until
+ * their bytes reach MH_PB_GROUP_RATIO (default 16384; 0: every chunk alone)
+ * times their longest message: one lane reads one message, so a launch lasts
+ * as long as its longest message however few it holds.  status[p] is exactly mh_dual_proof_pb_decode_batch's status for
+ * message p: MH_OK, MH_ERR_CORRUPTED_DATA, or MH_ERR_ILLEGAL_ARGUMENTS (a
+ * header or the linear proof missing).  ok[p] is 1 iff status[p] == MH_OK and
+ * Go's VerifyDualProof(proof, src[p], tgt[p], src_alh[32 p], tgt_alh[32 p])
+ * returns true on the decoded proof, i.e. mh_verify_dual_proof_batch's
+ * verdict, except that a version-0 header's metadata is ignored, as Go's
+ * innerHash ignores it (tx.go:258-263); a header version above 1 gives
+ * ok = 0.  A message without LinearAdvanceProof is verified as Go verifies a
+ * nil one (true only where verification.go:90-97 needs none): nothing is
+ * fetched, FillMissingLinearAdvanceProof is the caller's business.  n == 0
+ * returns MH_OK; null pointers, a non-monotonic msg_off and n above the limits
+ * of the V2 call (n <= 8 013 008) return MH_ERR_ILLEGAL_ARGUMENTS. */
+int mh_verify_dual_proof_pb_batch(mh_ctx *ctx, uint64_t n, const uint8_t *msgs,
+                                  const uint64_t *msg_off, const uint64_t *src,
+                                  const uint64_t *tgt, const uint8_t *src_alh,
+                                  const uint8_t *tgt_alh, int32_t *status, uint8_t *ok);
 
 int mh_htree_inclusion_proof_pb_decode_batch(mh_ctx *ctx, uint64_t n, const uint8_t *msgs,
                                              const uint64_t *msg_off, uint64_t *leaf,
