@@ -197,6 +197,7 @@ struct Log2 {
 constexpr int kFixedThreads = 256;
 constexpr int kWaveLds = 8192;
 constexpr uint32_t kFixedMaxValLen = 1u << 24;  // see entries_fixed_supported
+constexpr uint32_t kFixedFastMaxValLen = 1u << 23;  // see k_entries_fixed<LPL, true>
 
 // Workgroup timeline probe points of k_entries_fixed (0: start, 3: first value
 // block hashed, 1: leaf phase done, 2: end); empty in the library, defined by
@@ -261,6 +262,52 @@ __device__ __forceinline__ void lds_block(const char *lds, int lane, bool two, i
     }
 }
 
+// ---- fast path of k_entries_fixed: val_len a multiple of 128, so every unit
+// is two blocks ("two" layout) and there is no tail block.
+//
+// The eight 32-bit lane offsets of a unit's DMAs for entry i of the lane
+// groups (clamp to the batch's last entry, stride multiply, XOR swizzle: the
+// terms dma_issue() rebuilds per unit), computed once per entry and kept in
+// VGPRs; the unit's byte offset goes into the load's scalar offset.
+__device__ __forceinline__ void fast_lane_offsets(uint32_t stride, uint32_t lim, int lpl, int i,
+                                                  int lane, uint32_t voff[8]) {
+    const uint32_t ln = (uint32_t)lane;
+    const uint32_t k2 = (ln & 7) ^ (ln >> 4);
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const uint32_t rel = min((uint32_t)((j * 8 + (ln >> 3)) * lpl + i), lim);
+        voff[j] = rel * stride + ((j & 1) ? (k2 ^ 4) : k2) * 16;
+    }
+}
+
+// One unit (8 x 1 KiB) through the wave's buffer descriptor: rsrc, the LDS
+// destinations and byte_off are wave-uniform (SGPRs, M0), so a DMA is one
+// s_mov m0 + one buffer_load_dwordx4 ... offen lds and no VALU.
+__device__ __forceinline__ void dma_issue_fast(__amdgpu_buffer_rsrc_t rsrc, char *lds,
+                                               const uint32_t voff[8], uint32_t byte_off) {
+#pragma unroll
+    for (int j = 0; j < 8; j++)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t *)(lds + j * 1024), 16,
+                                                 (int)voff[j], (int)byte_off, 0, 0);
+}
+
+// the four 16-byte chunks of one block: a = the lane's address of chunk 0
+// (loop-invariant); chunk c is at a ^ (c << 4), block 1 at a ^ 64
+__device__ __forceinline__ void lds_read4(const char *lds, uint32_t a, uint4 r[4]) {
+#pragma unroll
+    for (int c = 0; c < 4; c++) r[c] = *reinterpret_cast<const uint4 *>(lds + (a ^ (c << 4)));
+}
+
+__device__ __forceinline__ void swap_words(const uint4 r[4], uint32_t w[16]) {
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        w[4 * c + 0] = bswap(r[c].x);
+        w[4 * c + 1] = bswap(r[c].y);
+        w[4 * c + 2] = bswap(r[c].z);
+        w[4 * c + 3] = bswap(r[c].w);
+    }
+}
+
 // Per-lane work is a uniform sequence of SHA-256 compressions driven by a
 // small state machine with ONE generic compress() call site (plus one
 // compress_kw for the constant padding block): value blocks -> padding ->
@@ -269,18 +316,28 @@ __device__ __forceinline__ void lds_block(const char *lds, int lane, bool two, i
 // 64 round constants of only one inlined compression live in SGPRs.
 enum : int { OP_VALUE = 0, OP_TAIL, OP_DIGEST, OP_LEAF, OP_NODE1, OP_NODE2 };
 
-template <int LPL>
+// FAST (val_len % 128 == 0, 128 <= val_len <= kFixedFastMaxValLen): the value
+// loop with `two` / `rem` folded, the DMA through a buffer descriptor with no
+// VALU per unit, one LDS address register, every lane compressing (a lane
+// past its group's entries carries a state nothing reads), and the padding
+// block's K+W table from the host (kwt).
+template <int LPL, bool FAST>
 __global__ __launch_bounds__(kFixedThreads) void k_entries_fixed(
     const uint8_t *__restrict__ vals, uint32_t val_len, const uint8_t *__restrict__ keys,
     uint32_t key_len, int version, uint64_t n, uint8_t *__restrict__ hvals_out,
-    uint8_t *__restrict__ levels, LaneLevels la, int wg_levels) {
+    uint8_t *__restrict__ levels, LaneLevels la, int wg_levels, KWTable kwt) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
+    int wave = threadIdx.x >> 6;
+    // scalar wave index: the LDS destinations of the DMAs stay in SGPRs
+    if (FAST) wave = __builtin_amdgcn_readfirstlane(wave);
     // K+W of the constant padding block (value length % 64 == 0), shared by
     // all waves; read back as wave-uniform LDS broadcasts.
     uint32_t *kw_lds = reinterpret_cast<uint32_t *>(smem + (kFixedThreads / 64) * kWaveLds);
-    if (threadIdx.x == 0) {
+    if (FAST) {
+        // pad_block_kw(val_len) from the launcher, one word per lane
+        if (threadIdx.x < 64) kw_lds[threadIdx.x] = kwt.kw[threadIdx.x];
+    } else if (threadIdx.x == 0) {
         // constant schedule of the padding block: 0x80, zeros, 64-bit bit length
         uint32_t w[16];
 #pragma unroll
@@ -313,8 +370,39 @@ __global__ __launch_bounds__(kFixedThreads) void k_entries_fixed(
     State s;
     s.init();
     uint32_t A[8], B[8], ny7 = 0;
+    // FAST: the wave's buffer descriptor and the per-entry lane offsets.
+    // Base = the wave's first entry e0; num_records = the bytes of vals from
+    // there (0 for an idle wave, which issues no load), capped at 2^32 - 1.
+    // A lane offset is at most rel * val_len + 112 with rel <= 64 * LPL - 1 <=
+    // 255, the unit offset at most val_len - 128, so voffset + soffset + 16 <=
+    // 256 * val_len <= 2^31 (val_len <= kFixedFastMaxValLen = 2^23): no 32-bit
+    // wrap, and with rel <= lim every load ends at or before (lim + 1) *
+    // val_len = the bytes that remain, i.e. inside num_records.  The inputs
+    // are wave-uniform; readfirstlane tells the compiler so (64-bit products
+    // are formed on the vector side), which keeps the descriptor in SGPRs.
+    const bool fast_busy = FAST && wave_busy;
+    const uint64_t e0 = fast_busy ? wave_slot0 * LPL : 0;
+    const uint64_t ents = fast_busy ? n - e0 : 0;  // entries from e0 on, >= 1 when busy
+    const uint32_t lim = ents - 1 < 0xffffffffull ? (uint32_t)(ents - 1) : 0xffffffffu;  // last rel.
+    const uint64_t left = ents * val_len < 0xffffffffull ? ents * val_len : 0xffffffffull;
+    const uint64_t base = (uint64_t)vals + e0 * val_len;
+    const uint64_t base_s =
+        ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32) |
+        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        (void *)base_s, 0, __builtin_amdgcn_readfirstlane((int)(uint32_t)left), 0x00020000);
+    uint32_t voff[8];
+    // the lane's LDS address of chunk 0 of block 0, from smem (kWaveLds is a
+    // multiple of 128, so the chunk / block XORs do not touch the wave part)
+    const uint32_t lds_a0 =
+        (uint32_t)wave * kWaveLds + (uint32_t)lane * 128 + ((((uint32_t)lane >> 1) & 7) << 4);
     if (wave_busy) {
+    if (FAST) {
+        fast_lane_offsets(val_len, lim, LPL, 0, lane, voff);
+        dma_issue_fast(rsrc, lds, voff, 0);
+    } else {
     if (units) dma_issue(vals, val_len, wave_slot0, LPL, 0, n, 0, nsteps2 > 0, lds, lane);
+    }
 
     int i = 0;         // entry of the lane group (uniform)
     uint32_t b = 0;    // value block (uniform)
@@ -324,6 +412,42 @@ __global__ __launch_bounds__(kFixedThreads) void k_entries_fixed(
     for (;;) {
         const uint64_t idx = first + i;
         bool on = i < c;
+        if (op == OP_VALUE && FAST) {
+            // One block per iteration through ONE compress site (a second
+            // site in this loop doubles its code and costs the contended
+            // headline more than the hidden LDS wait returns:
+            // profiles/ab_fixed_loop.txt).  Once block 1's reads have landed
+            // the whole unit is in registers and the next unit's DMA
+            // overwrites the buffer under block 1's rounds; the next entry's
+            // first unit is issued after the loop and lands under the
+            // padding / digest / leaf blocks.
+#pragma unroll 1
+            for (uint32_t bb = 0; bb < nfull; bb++) {
+                uint4 r[4];
+                uint32_t w[16];
+                // one address register: the empty asm keeps the compiler from
+                // holding all eight chunk addresses live across the kernel
+                // (a v_xor each per block instead)
+                uint32_t a = lds_a0;
+                asm volatile("" : "+v"(a));
+                lds_read4(smem, a ^ ((bb & 1) << 6), r);
+                if (bb & 1) {
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    const uint32_t u1 = (bb >> 1) + 1;
+                    if (u1 < units) dma_issue_fast(rsrc, lds, voff, u1 * 128);
+                }
+                swap_words(r, w);
+                compress(s, w);
+                if (bb == 0 && i == 0) MH_WG_PROBE(3);
+            }
+            if (i + 1 < LPL) {
+                fast_lane_offsets(val_len, lim, LPL, i + 1, lane, voff);
+                dma_issue_fast(rsrc, lds, voff, 0);
+            }
+            if (on) compress_kw(s, kw_lds);
+            op = OP_DIGEST;
+            continue;
+        }
         if (op == OP_VALUE) {
             // tight loop over the value's full blocks: its own compress site,
             // no state-machine dispatch per block
@@ -796,17 +920,23 @@ hipError_t launch_entries_fixed(hipStream_t st, Timer *tm, int version, uint64_t
     // the end of the leaf kernel.
     int wgl = 1;
     if (const char *e = getenv("MH_WG_LEVELS")) wgl = std::max(0, std::min(8, atoi(e)));
+    // Values of whole 128-byte units take the fast instantiation;
+    // MH_FIXED_FAST=0 keeps every shape on the general one (A/B in one build).
+    bool fast = val_len >= 128 && val_len % 128 == 0 && val_len <= kFixedFastMaxValLen;
+    if (const char *e = getenv("MH_FIXED_FAST"))
+        if (atoi(e) == 0) fast = false;
+    KWTable kwt = {};
+    if (fast) pad_block_kw(val_len, &kwt);
+    auto kernel = fast ? (lpl == 4   ? k_entries_fixed<4, true>
+                          : lpl == 2 ? k_entries_fixed<2, true>
+                                     : k_entries_fixed<1, true>)
+                       : (lpl == 4   ? k_entries_fixed<4, false>
+                          : lpl == 2 ? k_entries_fixed<2, false>
+                                     : k_entries_fixed<1, false>);
     {
         TimerScope ts(tm, "entries_fixed", st);
-        if (lpl == 4)
-            hipLaunchKernelGGL(k_entries_fixed<4>, dim3(grid), dim3(kFixedThreads), lds, st, vals,
-                               val_len, keys, key_len, version, n, hvals_out, levels, la, wgl);
-        else if (lpl == 2)
-            hipLaunchKernelGGL(k_entries_fixed<2>, dim3(grid), dim3(kFixedThreads), lds, st, vals,
-                               val_len, keys, key_len, version, n, hvals_out, levels, la, wgl);
-        else
-            hipLaunchKernelGGL(k_entries_fixed<1>, dim3(grid), dim3(kFixedThreads), lds, st, vals,
-                               val_len, keys, key_len, version, n, hvals_out, levels, la, wgl);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kFixedThreads), lds, st, vals, val_len, keys,
+                           key_len, version, n, hvals_out, levels, la, wgl, kwt);
     }
     *levels_done = std::min((lpl == 4 ? 2 : lpl == 2 ? 1 : 0) + wgl, g.nlevels - 1);
     return hipGetLastError();
