@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <condition_variable>
 #include <deque>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <thread>
@@ -449,6 +450,81 @@ inline hipError_t ensure_chunk_events(mh_ctx *c, size_t n) {
     return hipSuccess;
 }
 
+// The frame of the fused wire verifies (pb_decode.hip: DualProofV2 and
+// DualProof v1 messages, with the ids and Alh values to verify them against).
+// The call is bound by the copy of the messages (1.8 GB for 10^6 DualProofV2
+// at ~54 GB/s against ~11.5 ms of device work), so the batch is cut into
+// chunks of MH_PB_CHUNK_MIB of messages (default 128): a ChunkCopier issues
+// every chunk's copies on the context's copy stream and records one event per
+// chunk, while the caller decodes and verifies chunk k on the compute stream
+// as soon as its event fires -- only the last chunk's device work is exposed.
+// open() checks the arguments, takes c->mu (held until the frame goes out of
+// scope: declare the ChunkCopier after it), cuts the batch and makes the
+// events; fill() lists the copies once the caller has laid out its buffer.
+struct PbChunkFrame {
+    std::unique_lock<std::mutex> lk;
+    uint64_t n = 0, m0 = 0, mb = 0;  // messages, msg_off[0], message bytes
+    uint64_t chunk_bytes = 128ull << 20;
+    std::vector<uint64_t> cut{0};    // chunk k holds messages [cut[k], cut[k + 1])
+    std::vector<uint64_t> longest;   // each chunk's longest message
+    int nch = 0;
+    const uint8_t *msgs = nullptr, *src_alh = nullptr, *tgt_alh = nullptr;
+    const uint64_t *msg_off = nullptr, *src = nullptr, *tgt = nullptr;
+
+    // n > 0; have_outs: the caller's result pointers are all there
+    int open(mh_ctx *c, uint64_t n_, const uint8_t *msgs_, const uint64_t *msg_off_,
+             const uint64_t *src_, const uint64_t *tgt_, const uint8_t *src_alh_,
+             const uint8_t *tgt_alh_, bool have_outs) {
+        if (!msg_off_ || !src_ || !tgt_ || !src_alh_ || !tgt_alh_ || !have_outs)
+            return MH_ERR_ILLEGAL_ARGUMENTS;
+        n = n_, msgs = msgs_, msg_off = msg_off_, src = src_, tgt = tgt_;
+        src_alh = src_alh_, tgt_alh = tgt_alh_;
+        // a header's md_off is 32 bits over 2 n metadata slots
+        if (2 * n * (uint64_t)MH_MAX_TX_METADATA_LEN > 0xffffffffull) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (n > 0x7fffffffull) return MH_ERR_ILLEGAL_ARGUMENTS;  // hipcub's int item count
+        if (!monotonic(msg_off, n)) return MH_ERR_ILLEGAL_ARGUMENTS;
+        m0 = msg_off[0], mb = msg_off[n] - m0;
+        if (mb && !msgs) return MH_ERR_ILLEGAL_ARGUMENTS;
+        lk = std::unique_lock<std::mutex>(c->mu);
+        MH_HIP(hipSetDevice(c->device));
+        MH_HIP(c->copy_lane());
+        MH_HIP(c->p_small.ensure(64));
+        // chunks: consecutive messages up to chunk_bytes (one at least)
+        if (const char *e = getenv("MH_PB_CHUNK_MIB")) chunk_bytes = std::max(1, atoi(e)) * (1ull << 20);
+        for (uint64_t i = 0; i < n;) {
+            uint64_t j = i + 1, lm = msg_off[i + 1] - msg_off[i];
+            while (j < n && msg_off[j + 1] - msg_off[i] <= chunk_bytes) {
+                lm = std::max(lm, msg_off[j + 1] - msg_off[j]);
+                j++;
+            }
+            cut.push_back(j);
+            longest.push_back(lm);
+            i = j;
+        }
+        nch = (int)cut.size() - 1;
+        MH_HIP(ensure_chunk_events(c, nch));
+        return MH_OK;
+    }
+    // chunk 0 carries the per-message arrays whole (offsets, ids, Alh values,
+    // sources then targets at d_alh: few large copies -- each copy call costs
+    // the DMA engine ~0.1 ms of setup) and the first messages, chunk k its
+    // messages; message byte msg_off[i] lands at d_msg + msg_off[i] - m0
+    void fill(ChunkCopier &cc, uint8_t *d_msg, uint8_t *d_off, uint8_t *d_src, uint8_t *d_tgt,
+              uint8_t *d_alh) const {
+        cc.chunks.resize(nch);
+        cc.chunks[0] = {{d_off, msg_off, (n + 1) * 8},
+                        {d_src, src, n * 8},
+                        {d_tgt, tgt, n * 8},
+                        {d_alh, src_alh, n * 32},
+                        {d_alh + n * 32, tgt_alh, n * 32}};
+        for (int k = 0; k < nch; k++) {
+            const uint64_t lo = cut[k], hi = cut[k + 1];
+            cc.chunks[k].push_back({d_msg + (msg_off[lo] - m0), msgs + msg_off[lo],
+                                    msg_off[hi] - msg_off[lo]});
+        }
+    }
+};
+
 // events for the results of n groups in c->ev_results: default flags, i.e.
 // WITH the system-scope release -- the copies that wait on them may read the
 // results through a DMA engine rather than a kernel
@@ -576,6 +652,21 @@ int dual_proof_v2_core(mh_ctx *c, uint64_t n, const mh_tx_header *sh, const mh_t
                        const uint8_t *cons_terms, const uint64_t *src, const uint64_t *tgt,
                        const uint8_t *src_alh, const uint8_t *tgt_alh, int32_t *status,
                        bool alh_checked);
+// VerifyDualProof (v1, verification.go:127-235) over nk decoded proofs that
+// are on the device already (capi_tx.hip): THE statement of the v1 verifier,
+// behind both mh_verify_dual_proof_batch (the caller's arrays, uploaded) and
+// mh_verify_dual_proof_pb_batch (the decoder's arrays).  src / tgt / src_alh /
+// tgt_alh / ok: device, nk entries; status (device, nullable): proofs whose
+// decode status is not MH_OK are false; md_blob_len: the bytes behind
+// o.md_blob; v0_md: the callers' one difference (Dp1V0Metadata); Q: nested
+// proofs, o.off[kQ][nk] - o.off[kQ][0]; scratch: dual_proof_v1_scratch_bytes(
+// nk, Q) device bytes, 256-byte aligned.  Only launches on st: no copy from or
+// to the host, no synchronisation.
+uint64_t dual_proof_v1_scratch_bytes(uint64_t nk, uint64_t Q);
+int dual_proof_v1_core(hipStream_t st, Timer *tm, uint64_t nk, const Dual1Arrays &o,
+                       const uint64_t *src, const uint64_t *tgt, const uint8_t *src_alh,
+                       const uint8_t *tgt_alh, const int32_t *status, uint64_t md_blob_len,
+                       Dp1V0Metadata v0_md, uint64_t Q, uint8_t *scratch, uint8_t *ok);
 int build_many_dev(mh_ctx *c, hipStream_t st, uint64_t ntrees, const uint64_t *leaf_off,
                    const uint8_t *d_dig, uint8_t *d_roots, DevBuf &s_lv, DevBuf &s_lo);
 int run_tree_plan(mh_ctx *c, hipStream_t st, const TreePlan &P, uint64_t ntrees, uint64_t nleaves,

@@ -227,18 +227,72 @@ hipError_t launch_linear_verify(hipStream_t st, Timer *tm, uint64_t n, const uin
                                 const uint64_t *ptgt, const uint64_t *src, const uint64_t *tgt,
                                 const uint64_t *term_off, const uint8_t *terms,
                                 const uint8_t *src_alh, const uint8_t *tgt_alh, uint8_t *ok);
-hipError_t launch_advance_chain(hipStream_t st, Timer *tm, uint64_t n, const uint64_t *start,
-                                const uint64_t *cnt, const uint64_t *term_off,
-                                const uint8_t *terms, const uint64_t *first,
-                                const uint8_t *end_alh, uint8_t *leaves_src, uint8_t *ok);
-// the same chain over every proof of a batch, uncompacted: lane p runs only
-// when state[p] == 0 (its lengths checked by whoever set the state) and
-// otherwise reads no term and writes ok[p] = 0
+// the VerifyLinearAdvanceProof chain over every proof of a batch: lane p runs
+// only when state[p] == 0 (its lengths checked by whoever set the state) and
+// otherwise reads no term and writes ok[p] = 0.  first: the proofs' nested
+// offsets (n + 1); leaves_src is indexed from first[0]
 hipError_t launch_advance_chain_gated(hipStream_t st, Timer *tm, uint64_t n, const uint8_t *state,
                                       const uint64_t *start, const uint64_t *cnt,
                                       const uint64_t *term_off, const uint8_t *terms,
                                       const uint64_t *first, const uint8_t *end_alh,
                                       uint8_t *leaves_src, uint8_t *ok);
+
+// ---- VerifyDualProof (v1, verification.go:127-235) over device arrays
+// Per-proof counts of a DualProof (v1) and the CSR offset arrays scanned from
+// them: the five term lists, the nested InclusionProofs of the advance proof
+// and their terms, the canonical metadata bytes.
+enum : int { kI = 0, kC, kL, kLin, kAdv, kQ, kQT, kMd, kCounts };
+
+// A batch of decoded DualProofs on the device, in the layout of
+// mh_dual_proof_batch: what the decoder's write pass (pb_decode.hip) fills and
+// what dual_proof_v1_core (capi_tx.hip) verifies.  off[j] has n + 1 entries
+// and need not start at 0: terms[j] + 32 * off[j][p] is proof p's first term,
+// so a caller whose offsets start at off[j][0] passes terms[j] biased by
+// -32 * off[j][0].  off[kQ] are the proofs' first nested proofs
+// (advance_incl_first); qoff holds off[kQ][n] - off[kQ][0] + 1 term offsets,
+// entry 0 for nested proof off[kQ][0], into qterms (biased like terms[]).
+// off[kQT] and off[kMd] are the decoder's own (null for any other caller).
+struct Dual1Arrays {
+    const uint64_t *off[kCounts];
+    uint8_t *terms[5];  // incl, cons, last, linear, advance
+    uint8_t *qterms;
+    uint64_t *qoff;
+    mh_tx_header *src_hdr, *tgt_hdr;
+    uint8_t *md_blob;  // null: no blob, every header with metadata is refused
+    uint8_t *tbl_alh, *has_lin, *has_adv;
+    uint64_t *lin_src, *lin_tgt;
+};
+
+// The one intended difference between the callers of the v1 verifier: what a
+// v0 header that carries metadata means.  Go's innerHash never reads a v0
+// header's metadata (tx.go:258-263), so for headers decoded from the wire it
+// is dropped and the proof goes on; the array call keeps check_header's rule
+// (MH_ERR_METADATA_UNSUPPORTED) and the proof is false.
+enum Dp1V0Metadata : int { kDp1V0MetadataDropped = 0, kDp1V0MetadataRefused = 1 };
+
+struct Dp1Ops {        // per-proof operands of one batch (n entries unless noted)
+    mh_tx_header *hh;  // 2 n: the headers the Alh kernel hashes, sources then targets
+    uint8_t *x;        // 2 n x 32: the caller's Alh values in the same order
+    uint8_t *sbl, *tbl, *lin_sa, *end_alh;  // x 32
+    uint64_t *ii, *ij, *ci, *ls, *a_start, *a_cnt;
+    uint8_t *alive, *a_state;  // a_state: 0 run the chain, 1 true, 2 false
+};
+// argument checks + operands (k_dp1_prep); status may be null (every proof decoded)
+hipError_t launch_dp1_prep(hipStream_t st, Timer *tm, uint64_t n, const Dual1Arrays &o,
+                           const uint64_t *src, const uint64_t *tgt, const uint8_t *src_alh,
+                           const uint8_t *tgt_alh, const int32_t *status, uint64_t md_blob_len,
+                           Dp1V0Metadata v0_md, const Dp1Ops &w);
+// operands of the nq nested inclusion proofs, indexed from first[0]
+hipError_t launch_dp1_nested(hipStream_t st, Timer *tm, uint64_t nq, uint64_t n,
+                             const uint64_t *first, const Dp1Ops &w, uint64_t *qi, uint64_t *qj,
+                             uint8_t *qroot);
+struct Dp1Results {  // per-check results: n each, qok per nested proof from first[0]
+    const int32_t *ast;  // 2 n
+    const uint8_t *oki, *okc, *okl, *oklin, *aok, *qok;
+};
+hipError_t launch_dp1_verdict(hipStream_t st, Timer *tm, uint64_t n, const Dp1Ops &w,
+                              const Dp1Results &r, const uint8_t *has_lin, const uint64_t *first,
+                              uint8_t *ok);
 // roots of many htrees (widths leaf_off[t+1]-leaf_off[t], small), one lane
 // each, in place over nodes = their leaf hashes back to back
 constexpr uint64_t kSmallTreeMax = 64;

@@ -361,26 +361,17 @@ __global__ __launch_bounds__(256) void k_pbd_incl(uint64_t n, const uint8_t *__r
 // DualProofFromProto (database_protoconv.go:213-224) with LinearProofFromProto
 // (:264-270; not nil-checked: a message without linearProof panics in Go ->
 // MH_ERR_ILLEGAL_ARGUMENTS) and LinearAdvanceProofFromProto (:272-287; nil ->
-// has_advance 0; only the nested InclusionProofs' terms are kept).
-enum : int { kI = 0, kC, kL, kLin, kAdv, kQ, kQT, kMd, kCounts };  // per-message counts
-
-struct Dual1Out {  // device-side outputs of the write pass
-    const uint64_t *off[kCounts];  // scanned offsets (n + 1 each)
-    uint8_t *terms[5];             // incl, cons, last, linear, advance
-    uint8_t *qterms;               // nested inclusion proofs' terms
-    uint64_t *qoff;                // nested proofs' term offsets
-    mh_tx_header *src_hdr, *tgt_hdr;
-    uint8_t *md_blob, *tbl_alh, *has_lin, *has_adv;
-    uint64_t *lin_src, *lin_tgt;
-};
-
+// has_advance 0; only the nested InclusionProofs' terms are kept).  The
+// per-message counts (kI .. kMd) and the arrays the write pass fills
+// (Dual1Arrays, offsets from 0) are declared in mh_internal.hpp.
 template <bool WRITE>
 __global__ __launch_bounds__(256) void k_pbd_dual1(uint64_t n, const uint8_t *__restrict__ msgs,
                                                    const uint64_t *__restrict__ msg_off,
                                                    uint64_t *__restrict__ cnt,  // kCounts x n
-                                                   Dual1Out o, int32_t *__restrict__ status) {
+                                                   Dual1Arrays o, int32_t *__restrict__ status) {
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
+    if (WRITE && p == 0) o.qoff[o.off[kQ][n]] = o.off[kQT][n];  // the nested proofs' closing offset
     const uint64_t o0 = msg_off[p], o1 = msg_off[p + 1] >= o0 ? msg_off[p + 1] : o0;
     const bool corrupt = WRITE && status[p] == MH_ERR_CORRUPTED_DATA;
     mh_tx_header *hs = WRITE ? o.src_hdr + p : nullptr, *ht = WRITE ? o.tgt_hdr + p : nullptr;
@@ -585,10 +576,6 @@ __global__ void k_put2_host(const uint64_t *__restrict__ a, const uint64_t *__re
     }
 }
 
-// ------------------------------------------- DualProof (v1) from the wire, verified
-// The host loops of mh_verify_dual_proof_batch as kernels over the arrays the
-// write pass of k_pbd_dual1 left on the device.
-
 // The seven term / proof totals of a chunk (entry n of each scanned offset
 // array, kI .. kQT) into pinned host memory, as k_put2_host does for two.
 // so holds the kCounts offset arrays back to back, n + 1 entries each.
@@ -597,139 +584,6 @@ __global__ void k_put7_host(const uint64_t *__restrict__ so, uint64_t n, volatil
         out[threadIdx.x] = so[(uint64_t)threadIdx.x * (n + 1) + n];
         __threadfence_system();
     }
-}
-
-__device__ __forceinline__ void copy32(uint8_t *d, const uint8_t *s) {  // both 8-byte aligned
-    const uint2 *a = (const uint2 *)s;
-    uint2 *b = (uint2 *)d;
-#pragma unroll
-    for (int i = 0; i < 4; i++) b[i] = a[i];
-}
-
-struct Dp1Ops {      // per-proof operands of one chunk (n_k entries unless noted)
-    mh_tx_header *hh;  // 2 n_k: the headers the Alh kernel hashes, sources then targets
-    uint8_t *x;        // 2 n_k x 32: the caller's Alh values in the same order
-    uint8_t *sbl, *tbl, *lin_sa, *end_alh;  // x 32
-    uint64_t *ii, *ij, *ci, *ls, *a_start, *a_cnt;
-    uint8_t *alive, *a_state;  // a_state: 0 run the chain, 1 true, 2 false
-};
-
-// VerifyDualProof's argument checks (verification.go:128-138) and the
-// operands of every later check, one proof per lane.  A v0 header's metadata
-// is dropped (innerHash never reads it, tx.go:258-263); a header that cannot
-// be hashed (version > 1) kills the proof and is hashed as an empty v1 header
-// so that the Alh kernel's reads stay inside md_blob.  The advance proof's
-// state is verification.go:90-104 with both lengths taken from the decoded
-// offsets: state 0 promises the chain kernel end - start terms and the nested
-// kernels end - start - 1 proofs, all inside this message's own ranges.
-__global__ __launch_bounds__(256) void k_dp1_prep(uint64_t n, Dual1Out o,
-                                                  const uint64_t *__restrict__ src,
-                                                  const uint64_t *__restrict__ tgt,
-                                                  const uint8_t *__restrict__ src_alh,
-                                                  const uint8_t *__restrict__ tgt_alh,
-                                                  const int32_t *__restrict__ status, Dp1Ops w) {
-    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    if (p == 0) o.qoff[o.off[kQ][n]] = o.off[kQT][n];  // the nested proofs' closing offset
-    // headers read field by field and copied memory to memory: a header held
-    // in a local struct lands in scratch
-    const mh_tx_header *sh = o.src_hdr + p, *th = o.tgt_hdr + p;
-    const uint64_t s = src[p], t = tgt[p], sid = sh->id, tid = th->id, sbl_id = sh->bl_tx_id;
-    const uint32_t sv = sh->version, tv = th->version;
-    const bool alive = status[p] == MH_OK && sid == s && tid == t && sid != 0 && sid <= tid &&
-                       sv <= 1 && tv <= 1;
-    const uint64_t tbl_id = th->bl_tx_id;
-    const bool a_branch = s < tbl_id;  // verification.go:191 vs :211
-    const uint8_t *sa = src_alh + 32 * p, *tba = o.tbl_alh + 32 * p;
-    w.alive[p] = alive;
-    w.ii[p] = s;
-    w.ij[p] = tbl_id;
-    w.ci[p] = sbl_id;
-    w.ls[p] = a_branch ? tbl_id : s;
-    copy32(w.x + 32 * p, sa);
-    copy32(w.x + 32 * (n + p), tgt_alh + 32 * p);
-    copy32(w.sbl + 32 * p, sh->bl_root);
-    copy32(w.tbl + 32 * p, th->bl_root);
-    copy32(w.lin_sa + 32 * p, a_branch ? tba : sa);
-    copy32(w.end_alh + 32 * p, a_branch ? sa : tba);
-    const uint64_t start = sbl_id, end = a_branch ? s : tbl_id;
-    uint8_t state;
-    if (end < start) state = 2;
-    else if (end <= start + 1) state = 1;
-    else if (!o.has_adv[p] || o.off[kAdv][p + 1] - o.off[kAdv][p] != end - start ||
-             o.off[kQ][p + 1] - o.off[kQ][p] != end - start - 1)
-        state = 2;
-    else state = 0;
-    w.a_state[p] = state;
-    w.a_start[p] = start;
-    w.a_cnt[p] = state == 0 ? end - start - 1 : 0;
-    static_assert(sizeof(mh_tx_header) % 8 == 0, "headers are copied in 8-byte words");
-    const uint2 *hs = (const uint2 *)sh, *ht = (const uint2 *)th;
-    uint2 *ds = (uint2 *)(w.hh + p), *dd = (uint2 *)(w.hh + n + p);
-#pragma unroll
-    for (uint32_t i = 0; i < sizeof(mh_tx_header) / 8; i++) {
-        ds[i] = hs[i];
-        dd[i] = ht[i];
-    }
-    if (!alive) w.hh[p].version = w.hh[n + p].version = 1;
-    if (!alive || sv == 0) w.hh[p].md_len = 0;
-    if (!alive || tv == 0) w.hh[n + p].md_len = 0;
-}
-
-// Operands of nested InclusionProof q (verification.go:108-115), one lane per
-// q: its proof p is the one with off[kQ][p] <= q < off[kQ][p + 1].  The q of a
-// proof whose chain is not run gets i = j = 0, which the ahtree kernel
-// rejects before it reads a term.
-__global__ __launch_bounds__(256) void k_dp1_nested(uint64_t nq, uint64_t n,
-                                                    const uint64_t *__restrict__ first,
-                                                    const uint8_t *__restrict__ a_state,
-                                                    const uint64_t *__restrict__ a_start,
-                                                    const uint64_t *__restrict__ ij,
-                                                    const uint8_t *__restrict__ tbl,
-                                                    uint64_t *__restrict__ qi, uint64_t *__restrict__ qj,
-                                                    uint8_t *__restrict__ qroot) {
-    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= nq) return;
-    uint64_t lo = 0, hi = n;  // first[lo] <= q < first[hi] throughout
-    while (hi - lo > 1) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (first[mid] <= q) lo = mid;
-        else hi = mid;
-    }
-    const bool run = a_state[lo] == 0;
-    qi[q] = run ? a_start[lo] + 1 + (q - first[lo]) : 0;
-    qj[q] = run ? ij[lo] : 0;
-    copy32(qroot + 32 * q, tbl + 32 * lo);
-}
-
-// The verdict (the last loop of mh_verify_dual_proof_batch), one proof per
-// lane, the AND over its nested proofs included.
-__global__ __launch_bounds__(256) void k_dp1_verdict(
-    uint64_t n, const uint8_t *__restrict__ alive, const int32_t *__restrict__ ast,
-    const uint64_t *__restrict__ ii, const uint64_t *__restrict__ ij, const uint64_t *__restrict__ ci,
-    const uint8_t *__restrict__ oki, const uint8_t *__restrict__ okc, const uint8_t *__restrict__ okl,
-    const uint8_t *__restrict__ has_lin, const uint8_t *__restrict__ oklin,
-    const uint8_t *__restrict__ a_state, const uint64_t *__restrict__ a_cnt,
-    const uint64_t *__restrict__ first, const uint8_t *__restrict__ aok,
-    const uint8_t *__restrict__ qok, uint8_t *__restrict__ ok) {
-    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    bool r = alive[p] && ast[p] == MH_OK && ast[n + p] == MH_OK;
-    if (r && ii[p] < ij[p]) r = oki[p];
-    if (r && ci[p] > 0) r = okc[p];
-    if (r && ij[p] > 0) r = okl[p];
-    if (r) r = has_lin[p] && oklin[p];
-    if (r) {
-        const uint8_t state = a_state[p];
-        if (state == 0) {
-            r = aok[p];
-            const uint64_t f = first[p], c0 = a_cnt[p];
-            for (uint64_t x = 0; x < c0 && r; x++) r = qok[f + x];
-        } else {
-            r = state == 1;
-        }
-    }
-    ok[p] = r ? 1 : 0;
 }
 
 }  // namespace
@@ -922,7 +776,7 @@ extern "C" int mh_dual_proof_pb_decode_batch(mh_ctx *c, uint64_t n, const uint8_
         const uint8_t *dmsg = base + b_msg - m0;
         uint64_t *cnt = (uint64_t *)(base + b_cnt), *so = (uint64_t *)(base + b_so);
         hipLaunchKernelGGL(k_pbd_dual1<false>, dim3(grid), dim3(256), 0, st, n, dmsg,
-                           (const uint64_t *)(base + b_off), cnt, Dual1Out{},
+                           (const uint64_t *)(base + b_off), cnt, Dual1Arrays{},
                            (int32_t *)(base + b_st));
         MH_HIP(hipGetLastError());
         for (int j = 0; j < kCounts; j++) {
@@ -968,7 +822,7 @@ extern "C" int mh_dual_proof_pb_decode_batch(mh_ctx *c, uint64_t n, const uint8_
         MH_HIP(tb.ensure(tall * 32 + (nq + 1) * 8 + 8));
         uint8_t *dt = tb.as<uint8_t>();
         uint64_t *dq = (uint64_t *)(dt + tall * 32);
-        Dual1Out o;
+        Dual1Arrays o;
         for (int j = 0; j < kCounts; j++) o.off[j] = so + (uint64_t)j * (n + 1);
         for (int j = 0; j < 5; j++) o.terms[j] = dt + tpos[j] * 32;
         o.qterms = dt + tpos[5] * 32;
@@ -1000,52 +854,31 @@ extern "C" int mh_dual_proof_pb_decode_batch(mh_ctx *c, uint64_t n, const uint8_
         if (totals[kQT])
             MH_HIP(hipMemcpyAsync(out->advance_incl_terms, dt + tpos[5] * 32, totals[kQT] * 32,
                                   hipMemcpyDeviceToHost, st));
-        if (nq) MH_HIP(hipMemcpyAsync(out->advance_incl_off, dq, nq * 8, hipMemcpyDeviceToHost, st));
+        MH_HIP(hipMemcpyAsync(out->advance_incl_off, dq, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
         MH_HIP(hipStreamSynchronize(st));
-        out->advance_incl_off[nq] = totals[kQT];
         return MH_OK;
     });
 }
 
-// The fused call is bound by the copy of the messages (1.8 GB for 10^6
-// DualProofV2 at ~54 GB/s against ~11.5 ms of device work), so the batch is
-// cut into chunks of ~64 MiB of messages (MH_PB_CHUNK_MIB): a helper thread
-// issues every chunk's copies on the context's copy stream (a pageable copy
-// holds its issuing thread until it is staged) and records one event per
-// chunk, while this thread decodes and verifies chunk k on the compute stream
-// as soon as its event fires -- only the last chunk's device work is exposed.
+// DualProofV2 straight from the wire, in the chunk frame of PbChunkFrame
+// (capi_internal.hpp): chunk k is decoded and verified on the compute stream
+// as soon as its copy has landed.
 extern "C" int mh_verify_dual_proof_v2_pb_batch(mh_ctx *c, uint64_t n, const uint8_t *msgs,
                                                 const uint64_t *msg_off, const uint64_t *src,
                                                 const uint64_t *tgt, const uint8_t *src_alh,
                                                 const uint8_t *tgt_alh, int32_t *status) {
     return mh_guard([&]() -> int {
-        if (!c || (n && (!msg_off || !src || !tgt || !src_alh || !tgt_alh || !status)))
-            return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (!c) return MH_ERR_ILLEGAL_ARGUMENTS;
         if (n == 0) return MH_OK;
-        if (2 * n * (uint64_t)kMdSlot > 0xffffffffull) return MH_ERR_ILLEGAL_ARGUMENTS;  // md_off
-        if (n > 0x7fffffffull) return MH_ERR_ILLEGAL_ARGUMENTS;  // hipcub's int item count
-        if (!monotonic(msg_off, n)) return MH_ERR_ILLEGAL_ARGUMENTS;
-        const uint64_t m0 = msg_off[0], mb = msg_off[n] - m0;
-        if (mb && !msgs) return MH_ERR_ILLEGAL_ARGUMENTS;
-        std::lock_guard<std::mutex> lk(c->mu);
-        MH_HIP(hipSetDevice(c->device));
-        MH_HIP(c->copy_lane());
-        MH_HIP(c->p_small.ensure(64));
+        PbChunkFrame F;
+        if (int e = F.open(c, n, msgs, msg_off, src, tgt, src_alh, tgt_alh, status != nullptr))
+            return e;
+        const std::vector<uint64_t> &cut = F.cut;
+        const uint64_t m0 = F.m0, mb = F.mb, chunk_bytes = F.chunk_bytes;
+        const int nch = F.nch;
         hipStream_t st = c->stream;
-        // chunks: consecutive messages up to chunk_bytes (one at least)
-        uint64_t chunk_bytes = 128ull << 20;
-        if (const char *e = getenv("MH_PB_CHUNK_MIB")) chunk_bytes = std::max(1, atoi(e)) * (1ull << 20);
-        std::vector<uint64_t> cut{0};
-        for (uint64_t i = 0; i < n;) {
-            uint64_t j = i + 1;
-            while (j < n && msg_off[j + 1] - msg_off[i] <= chunk_bytes) j++;
-            cut.push_back(j);
-            i = j;
-        }
-        const int nch = (int)cut.size() - 1;
         uint64_t max_nk = 0;
         for (int k = 0; k < nch; k++) max_nk = std::max(max_nk, cut[k + 1] - cut[k]);
-        MH_HIP(ensure_chunk_events(c, nch));
         size_t scan_bytes = 0;
         MH_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const uint64_t *)nullptr,
                                                 (uint64_t *)nullptr, (int)max_nk, st));
@@ -1070,22 +903,8 @@ extern "C" int mh_verify_dual_proof_v2_pb_batch(mh_ctx *c, uint64_t n, const uin
         DevBuf &tb = c->s_tree;
         MH_HIP(tb.ensure(std::max<uint64_t>(std::min(mb, chunk_bytes) / 34 + 64, 1) * 32));
         uint8_t *base = c->s_tx.as<uint8_t>();
-        // the copies, one helper thread: chunk 0 = the per-message arrays
-        // whole (offsets, ids, Alh values: few large copies -- each copy call
-        // costs the DMA engine ~0.1 ms of setup) and the first messages, chunk
-        // k = its messages
         ChunkCopier cc(c);
-        cc.chunks.resize(nch);
-        cc.chunks[0] = {{base + b_off, msg_off, (n + 1) * 8},
-                        {base + b_src, src, n * 8},
-                        {base + b_tgt, tgt, n * 8},
-                        {base + b_xa, src_alh, n * 32},
-                        {base + b_xa + n * 32, tgt_alh, n * 32}};
-        for (int k = 0; k < nch; k++) {
-            const uint64_t lo = cut[k], hi = cut[k + 1];
-            const uint64_t b0 = msg_off[lo] - m0, bb = msg_off[hi] - msg_off[lo];
-            cc.chunks[k].push_back({base + b_msg + b0, msgs + msg_off[lo], bb});
-        }
+        F.fill(cc, base + b_msg, base + b_off, base + b_src, base + b_tgt, base + b_xa);
         MH_HIP(cc.start());
         const uint8_t *dmsg = base + b_msg - m0;
         int32_t *dst_all = (int32_t *)(base + b_st);
@@ -1166,48 +985,28 @@ extern "C" int mh_verify_dual_proof_v2_pb_batch(mh_ctx *c, uint64_t n, const uin
     });
 }
 
-// DualProof (v1) straight from the wire: the frame of the V2 call above
-// (chunks of MH_PB_CHUNK_MIB of messages copied on the copy lane, one event
-// each, decoded and verified on the compute stream while the next ones copy),
-// the decode of mh_dual_proof_pb_decode_batch into device scratch and the
-// checks of mh_verify_dual_proof_batch with every host loop replaced by a
-// kernel.  The per-proof scratch is sized for the largest group of chunks
-// (below) and reused group after group (one compute stream orders them);
-// only status and ok leave the device.
+// DualProof (v1) straight from the wire: the chunk frame of the V2 call above
+// (PbChunkFrame), the decode of mh_dual_proof_pb_decode_batch into device
+// scratch, then dual_proof_v1_core (capi_tx.hip) -- the verifier behind
+// mh_verify_dual_proof_batch too -- over the decoded arrays, with
+// kDp1V0MetadataDropped: a v0 header's metadata bytes are not hashed.  The
+// decode scratch is sized for the largest group of chunks (below) and reused
+// group after group (one compute stream orders them); only status and ok
+// leave the device.
 extern "C" int mh_verify_dual_proof_pb_batch(mh_ctx *c, uint64_t n, const uint8_t *msgs,
                                              const uint64_t *msg_off, const uint64_t *src,
                                              const uint64_t *tgt, const uint8_t *src_alh,
                                              const uint8_t *tgt_alh, int32_t *status, uint8_t *ok) {
     return mh_guard([&]() -> int {
-        if (!c || (n && (!msg_off || !src || !tgt || !src_alh || !tgt_alh || !status || !ok)))
-            return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (!c) return MH_ERR_ILLEGAL_ARGUMENTS;
         if (n == 0) return MH_OK;
-        if (2 * n * (uint64_t)kMdSlot > 0xffffffffull) return MH_ERR_ILLEGAL_ARGUMENTS;  // md_off
-        if (n > 0x7fffffffull) return MH_ERR_ILLEGAL_ARGUMENTS;  // hipcub's int item count
-        if (!monotonic(msg_off, n)) return MH_ERR_ILLEGAL_ARGUMENTS;
-        const uint64_t m0 = msg_off[0], mb = msg_off[n] - m0;
-        if (mb && !msgs) return MH_ERR_ILLEGAL_ARGUMENTS;
-        std::lock_guard<std::mutex> lk(c->mu);
-        MH_HIP(hipSetDevice(c->device));
-        MH_HIP(c->copy_lane());
-        MH_HIP(c->p_small.ensure(64));
+        PbChunkFrame F;
+        if (int e = F.open(c, n, msgs, msg_off, src, tgt, src_alh, tgt_alh, status && ok)) return e;
+        const std::vector<uint64_t> &cut = F.cut, &longest = F.longest;
+        const uint64_t m0 = F.m0, mb = F.mb;
+        const int nch = F.nch;
         hipStream_t st = c->stream;
         Timer *tm = c->tm();
-        // chunks: consecutive messages up to chunk_bytes (one at least)
-        uint64_t chunk_bytes = 128ull << 20;
-        if (const char *e = getenv("MH_PB_CHUNK_MIB")) chunk_bytes = std::max(1, atoi(e)) * (1ull << 20);
-        std::vector<uint64_t> cut{0}, longest;  // longest: each chunk's longest message
-        for (uint64_t i = 0; i < n;) {
-            uint64_t j = i + 1, lm = msg_off[i + 1] - msg_off[i];
-            while (j < n && msg_off[j + 1] - msg_off[i] <= chunk_bytes) {
-                lm = std::max(lm, msg_off[j + 1] - msg_off[j]);
-                j++;
-            }
-            cut.push_back(j);
-            longest.push_back(lm);
-            i = j;
-        }
-        const int nch = (int)cut.size() - 1;
         // groups: consecutive chunks decoded and verified by one set of
         // launches.  Every kernel here runs one message per lane, so a launch
         // lasts as long as its longest message takes one lane (~2.7 MB/s
@@ -1237,43 +1036,23 @@ extern "C" int mh_verify_dual_proof_pb_batch(mh_ctx *c, uint64_t n, const uint8_
         const int ng = (int)gcut.size() - 1;
         uint64_t M = 0;  // proofs of the largest group
         for (int g = 0; g < ng; g++) M = std::max(M, cut[gcut[g + 1]] - cut[gcut[g]]);
-        MH_HIP(ensure_chunk_events(c, nch));
         size_t scan_bytes = 0;
         MH_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const uint64_t *)nullptr,
                                                 (uint64_t *)nullptr, (int)M, st));
         Layout L;
-        // the caller's arrays and the results, whole; then one group's scratch
+        // the caller's arrays and the results, whole; then one group's decode
         const uint64_t b_msg = L.add(mb + 16), b_off = L.add((n + 1) * 8), b_src = L.add(n * 8),
                        b_tgt = L.add(n * 8), b_xa = L.add(2 * n * 32), b_st = L.add(n * 4),
                        b_ok = L.add(n);
         const uint64_t b_cnt = L.add(kCounts * M * 8), b_so = L.add(kCounts * (M + 1) * 8),
                        b_scan = L.add(scan_bytes), b_h = L.add(2 * M * sizeof(mh_tx_header)),
-                       b_hh = L.add(2 * M * sizeof(mh_tx_header)), b_md = L.add(2 * M * (uint64_t)kMdSlot),
-                       b_tba = L.add(M * 32), b_flags = L.add(2 * M), b_lsrc = L.add(2 * M * 8),
-                       b_s = L.add(2 * M * kTxInnerStride), b_x = L.add(2 * M * 32),
-                       b_ast = L.add(2 * M * 4), b_sbl = L.add(M * 32), b_tbl = L.add(M * 32),
-                       b_lsa = L.add(M * 32), b_end = L.add(M * 32), b_lfa = L.add(M * 32),
-                       b_lft = L.add(M * 32), b_ii = L.add(M * 8), b_ij = L.add(M * 8),
-                       b_ci = L.add(M * 8), b_ls = L.add(M * 8), b_ast0 = L.add(M * 8),
-                       b_acnt = L.add(M * 8), b_alive = L.add(M), b_astate = L.add(M),
-                       b_oki = L.add(M), b_okc = L.add(M), b_okl = L.add(M), b_oklin = L.add(M),
-                       b_aok = L.add(M);
+                       b_md = L.add(2 * M * (uint64_t)kMdSlot), b_tba = L.add(M * 32),
+                       b_flags = L.add(2 * M), b_lsrc = L.add(2 * M * 8);
         MH_HIP(c->s_tx.ensure(L.total));
         uint8_t *base = c->s_tx.as<uint8_t>();
         auto U = [&](uint64_t off) { return (uint64_t *)(base + off); };
-        // chunk 0 carries the per-message arrays whole, chunk k its messages
         ChunkCopier cc(c);
-        cc.chunks.resize(nch);
-        cc.chunks[0] = {{base + b_off, msg_off, (n + 1) * 8},
-                        {base + b_src, src, n * 8},
-                        {base + b_tgt, tgt, n * 8},
-                        {base + b_xa, src_alh, n * 32},
-                        {base + b_xa + n * 32, tgt_alh, n * 32}};
-        for (int k = 0; k < nch; k++) {
-            const uint64_t lo = cut[k], hi = cut[k + 1];
-            cc.chunks[k].push_back({base + b_msg + (msg_off[lo] - m0), msgs + msg_off[lo],
-                                    msg_off[hi] - msg_off[lo]});
-        }
+        F.fill(cc, base + b_msg, base + b_off, base + b_src, base + b_tgt, base + b_xa);
         MH_HIP(cc.start());
         const uint8_t *dmsg = base + b_msg - m0;
         int32_t *dst_all = (int32_t *)(base + b_st);
@@ -1292,7 +1071,7 @@ extern "C" int mh_verify_dual_proof_pb_batch(mh_ctx *c, uint64_t n, const uint8_
             {
                 TimerScope ts(tm, "pbd_dual1_size", st);
                 hipLaunchKernelGGL(k_pbd_dual1<false>, dim3(grid), dim3(256), 0, st, nk, dmsg, doff,
-                                   cnt, Dual1Out{}, dst);
+                                   cnt, Dual1Arrays{}, dst);
                 MH_HIP(hipGetLastError());
             }
             for (int j = 0; j < kCounts; j++) {
@@ -1312,18 +1091,17 @@ extern "C" int mh_verify_dual_proof_pb_batch(mh_ctx *c, uint64_t n, const uint8_
             MH_HIP(hipStreamSynchronize(st));
             uint64_t totals[kMd];
             for (int j = 0; j < kMd; j++) totals[j] = tot[j];
-            // term area: the five lists, the nested terms, the nested proofs'
-            // offsets and operands
+            // term area: the five lists, the nested terms and their offsets;
+            // then the verifier's scratch
             const uint64_t Q = totals[kQ];
             Layout T;
             uint64_t t_terms[5];
             for (int j = 0; j < 5; j++) t_terms[j] = T.add(totals[j] * 32);
             const uint64_t t_qt = T.add(totals[kQT] * 32), t_qo = T.add((Q + 1) * 8),
-                           t_qsrc = T.add(Q * 32), t_qleaf = T.add(Q * 32), t_qi = T.add(Q * 8),
-                           t_qj = T.add(Q * 8), t_qroot = T.add(Q * 32), t_qok = T.add(Q);
+                           t_core = T.add(dual_proof_v1_scratch_bytes(nk, Q));
             MH_HIP(tb.ensure(T.total + 8));
             uint8_t *dt = tb.as<uint8_t>();
-            Dual1Out o;
+            Dual1Arrays o;
             for (int j = 0; j < kCounts; j++) o.off[j] = so + (uint64_t)j * (nk + 1);
             for (int j = 0; j < 5; j++) o.terms[j] = dt + t_terms[j];
             o.qterms = dt + t_qt;
@@ -1343,69 +1121,12 @@ extern "C" int mh_verify_dual_proof_pb_batch(mh_ctx *c, uint64_t n, const uint8_
                 MH_HIP(hipGetLastError());
             }
             // VerifyDualProof (verification.go:127-235)
-            const uint64_t *dsrc = (const uint64_t *)(base + b_src) + lo,
-                           *dtgt = (const uint64_t *)(base + b_tgt) + lo;
-            const uint8_t *dsa = base + b_xa + lo * 32, *dta = base + b_xa + (n + lo) * 32;
-            Dp1Ops w;
-            w.hh = (mh_tx_header *)(base + b_hh);
-            w.x = base + b_x;
-            w.sbl = base + b_sbl;
-            w.tbl = base + b_tbl;
-            w.lin_sa = base + b_lsa;
-            w.end_alh = base + b_end;
-            w.ii = U(b_ii);
-            w.ij = U(b_ij);
-            w.ci = U(b_ci);
-            w.ls = U(b_ls);
-            w.a_start = U(b_ast0);
-            w.a_cnt = U(b_acnt);
-            w.alive = base + b_alive;
-            w.a_state = base + b_astate;
-            {
-                TimerScope ts(tm, "dp1_prep", st);
-                hipLaunchKernelGGL(k_dp1_prep, dim3(grid), dim3(256), 0, st, nk, o, dsrc, dtgt, dsa,
-                                   dta, (const int32_t *)dst, w);
-                MH_HIP(hipGetLastError());
-            }
-            int32_t *ast = (int32_t *)(base + b_ast);
-            // header Alh (:140-148)
-            MH_HIP(launch_tx_alh(st, tm, 2 * nk, w.hh, o.md_blob, nullptr, base + b_s, w.x, nullptr,
-                                 nullptr, nullptr, ast));
-            // inclusion / consistency / last inclusion (:150-189)
-            MH_HIP(launch_leaf_for(st, tm, nk, w.x, base + b_lfa));
-            MH_HIP(launch_leaf_for(st, tm, nk, o.tbl_alh, base + b_lft));
-            MH_HIP(launch_ahtree_verify(st, tm, MH_AHT_INCLUSION, nk, w.ii, w.ij, o.off[kI],
-                                        o.terms[kI], base + b_lfa, w.tbl, base + b_oki, nullptr));
-            MH_HIP(launch_ahtree_verify(st, tm, MH_AHT_CONSISTENCY, nk, w.ci, w.ij, o.off[kC],
-                                        o.terms[kC], w.sbl, w.tbl, base + b_okc, nullptr));
-            MH_HIP(launch_ahtree_verify(st, tm, MH_AHT_LAST_INCLUSION, nk, w.ij, w.ij, o.off[kL],
-                                        o.terms[kL], base + b_lft, w.tbl, base + b_okl, nullptr));
-            // linear proof (:192 / :213)
-            MH_HIP(launch_linear_verify(st, tm, nk, o.lin_src, o.lin_tgt, w.ls, dtgt, o.off[kLin],
-                                        o.terms[kLin], w.lin_sa, dta, base + b_oklin));
-            // linear advance proof: the chain, then the nested inclusion proofs
-            MH_HIP(launch_advance_chain_gated(st, tm, nk, w.a_state, w.a_start, w.a_cnt, o.off[kAdv],
-                                              o.terms[kAdv], o.off[kQ], w.end_alh, dt + t_qsrc,
-                                              base + b_aok));
-            if (Q) {
-                TimerScope ts(tm, "dp1_nested", st);
-                hipLaunchKernelGGL(k_dp1_nested, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st,
-                                   Q, nk, o.off[kQ], w.a_state, w.a_start, w.ij, w.tbl,
-                                   (uint64_t *)(dt + t_qi), (uint64_t *)(dt + t_qj), dt + t_qroot);
-                MH_HIP(hipGetLastError());
-            }
-            MH_HIP(launch_leaf_for(st, tm, Q, dt + t_qsrc, dt + t_qleaf));
-            MH_HIP(launch_ahtree_verify(st, tm, MH_AHT_INCLUSION, Q, (const uint64_t *)(dt + t_qi),
-                                        (const uint64_t *)(dt + t_qj), o.qoff, o.qterms,
-                                        dt + t_qleaf, dt + t_qroot, dt + t_qok, nullptr));
-            {
-                TimerScope ts(tm, "dp1_verdict", st);
-                hipLaunchKernelGGL(k_dp1_verdict, dim3(grid), dim3(256), 0, st, nk, w.alive, ast,
-                                   w.ii, w.ij, w.ci, base + b_oki, base + b_okc, base + b_okl,
-                                   o.has_lin, base + b_oklin, w.a_state, w.a_cnt, o.off[kQ],
-                                   base + b_aok, dt + t_qok, base + b_ok + lo);
-                MH_HIP(hipGetLastError());
-            }
+            if (int e = dual_proof_v1_core(st, tm, nk, o, (const uint64_t *)(base + b_src) + lo,
+                                           (const uint64_t *)(base + b_tgt) + lo,
+                                           base + b_xa + lo * 32, base + b_xa + (n + lo) * 32, dst,
+                                           2 * nk * (uint64_t)kMdSlot, kDp1V0MetadataDropped, Q,
+                                           dt + t_core, base + b_ok + lo))
+                return e;
         }
         MH_HIP(cc.join());
         MH_HIP(hipMemcpyAsync(status, dst_all, n * 4, hipMemcpyDeviceToHost, st));

@@ -178,20 +178,28 @@ __global__ __launch_bounds__(256) void k_linear_verify(
     ok[p] = res ? 1 : 0;
 }
 
-// VerifyLinearAdvanceProof chain (verification.go:106-121) for proofs that
-// passed the host-side length checks: calc starts at terms[0] (Alh of
-// start+1); before every advance the current calc is written to
-// leaves_src[first + k] (its leafFor must be included in the target tree at
-// index start+1+k), then calc = advanceLinearHash(calc, start+2+k, terms[k+1]).
-// ok[p] = (final calc == end_alh[p]).
-__global__ __launch_bounds__(256) void k_advance_chain(
-    uint64_t n, const uint64_t *__restrict__ start, const uint64_t *__restrict__ cnt,
-    const uint64_t *__restrict__ term_off, const uint8_t *__restrict__ terms,
-    const uint64_t *__restrict__ first, const uint8_t *__restrict__ end_alh,
-    uint8_t *__restrict__ leaves_src, uint8_t *__restrict__ ok) {
+// VerifyLinearAdvanceProof chain (verification.go:106-121) for every proof of
+// a batch (the three-way state of verification.go:90-104 stays on the
+// device, no proof is compacted away).  Lane p runs only when state[p] == 0,
+// which promises cnt[p] + 1 terms from term_off[p] and cnt[p] nested proofs
+// from first[p]; any other lane touches no term and no leaf.  calc starts at
+// terms[0] (Alh of start+1); before every advance the current calc is written
+// to leaves_src[first[p] - first[0] + k] (its leafFor must be included in the
+// target tree at index start+1+k), then calc = advanceLinearHash(calc,
+// start+2+k, terms[k+1]).  ok[p] = (final calc == end_alh[p]).
+__global__ __launch_bounds__(256) void k_advance_chain_gated(
+    uint64_t n, const uint8_t *__restrict__ state, const uint64_t *__restrict__ start,
+    const uint64_t *__restrict__ cnt, const uint64_t *__restrict__ term_off,
+    const uint8_t *__restrict__ terms, const uint64_t *__restrict__ first,
+    const uint8_t *__restrict__ end_alh, uint8_t *__restrict__ leaves_src,
+    uint8_t *__restrict__ ok) {
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
-    const uint64_t t0 = term_off[p], c0 = cnt[p], s = start[p], f = first[p];
+    if (state[p] != 0) {
+        ok[p] = 0;
+        return;
+    }
+    const uint64_t t0 = term_off[p], c0 = cnt[p], s = start[p], f = first[p] - first[0];
     uint32_t c[8], x[8];
     load_digest(terms + t0 * 32, c);
     for (uint64_t k = 0; k < c0; k++) {
@@ -207,37 +215,150 @@ __global__ __launch_bounds__(256) void k_advance_chain(
     ok[p] = d == 0;
 }
 
-// The same chain for every proof of a batch, none compacted away (the fused
-// wire verify keeps the three-way state of verification.go:90-104 on the
-// device): lane p runs the chain only when state[p] == 0, which promises
-// cnt[p] + 1 terms from term_off[p] and cnt[p] nested proofs from first[p];
-// any other lane touches no term and no leaf.
-__global__ __launch_bounds__(256) void k_advance_chain_gated(
-    uint64_t n, const uint8_t *__restrict__ state, const uint64_t *__restrict__ start,
-    const uint64_t *__restrict__ cnt, const uint64_t *__restrict__ term_off,
-    const uint8_t *__restrict__ terms, const uint64_t *__restrict__ first,
-    const uint8_t *__restrict__ end_alh, uint8_t *__restrict__ leaves_src,
-    uint8_t *__restrict__ ok) {
+// ------------------------------------------- VerifyDualProof (v1) around the checks
+// Everything of store.VerifyDualProof (verification.go:127-235) that is not a
+// hash: the argument checks and operands before the checks, the verdict after
+// them.  dual_proof_v1_core (capi_tx.hip) strings them together.
+
+__device__ __forceinline__ void copy32(uint8_t *d, const uint8_t *s) {  // both 8-byte aligned
+    const uint2 *a = (const uint2 *)s;
+    uint2 *b = (uint2 *)d;
+#pragma unroll
+    for (int i = 0; i < 4; i++) b[i] = a[i];
+}
+
+// check_header's rule (capi_internal.hpp) on a header's fields; v0_md: what a
+// v0 header with metadata means to this caller (Dp1V0Metadata)
+__device__ __forceinline__ bool dp1_header_ok(uint32_t version, uint32_t md_len, uint32_t md_off,
+                                              uint64_t md_blob_len, bool have_blob, int v0_md) {
+    if (version > 1) return false;
+    if (md_len == 0) return true;
+    if (version == 0) return v0_md == kDp1V0MetadataDropped;
+    return md_len <= MH_MAX_TX_METADATA_LEN && have_blob && (uint64_t)md_off + md_len <= md_blob_len;
+}
+
+// VerifyDualProof's argument checks (verification.go:128-138) and the
+// operands of every later check, one proof per lane.  A header that cannot be
+// hashed (dp1_header_ok) kills the proof; a dead proof's headers are hashed as
+// empty v1 headers so that the Alh kernel's reads stay inside md_blob, and so
+// is the metadata of every v0 header (innerHash never reads it, tx.go:258-263;
+// with kDp1V0MetadataRefused such a proof is dead already).  The advance
+// proof's state is verification.go:90-104 with both lengths taken from the
+// offsets: state 0 promises the chain kernel end - start terms and the nested
+// kernels end - start - 1 proofs, all inside this proof's own ranges.
+__global__ __launch_bounds__(256) void k_dp1_prep(uint64_t n, Dual1Arrays o,
+                                                  const uint64_t *__restrict__ src,
+                                                  const uint64_t *__restrict__ tgt,
+                                                  const uint8_t *__restrict__ src_alh,
+                                                  const uint8_t *__restrict__ tgt_alh,
+                                                  const int32_t *__restrict__ status,
+                                                  uint64_t md_blob_len, int v0_md, Dp1Ops w) {
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
-    if (state[p] != 0) {
-        ok[p] = 0;
-        return;
-    }
-    const uint64_t t0 = term_off[p], c0 = cnt[p], s = start[p], f = first[p];
-    uint32_t c[8], x[8];
-    load_digest(terms + t0 * 32, c);
-    for (uint64_t k = 0; k < c0; k++) {
-        store_digest(leaves_src + (f + k) * 32, c);
-        uint32_t term[8];
-        load_digest(terms + (t0 + k + 1) * 32, term);
-        alh_hash(s + 2 + k, c, term, c);
-    }
-    load_digest(end_alh + p * 32, x);
-    uint32_t d = 0;
+    // headers read field by field and copied memory to memory: a header held
+    // in a local struct lands in scratch
+    const mh_tx_header *sh = o.src_hdr + p, *th = o.tgt_hdr + p;
+    const uint64_t s = src[p], t = tgt[p], sid = sh->id, tid = th->id, sbl_id = sh->bl_tx_id;
+    const uint32_t sv = sh->version, tv = th->version;
+    const bool have_blob = o.md_blob != nullptr;
+    const bool alive = (!status || status[p] == MH_OK) && sid == s && tid == t && sid != 0 &&
+                       sid <= tid &&
+                       dp1_header_ok(sv, sh->md_len, sh->md_off, md_blob_len, have_blob, v0_md) &&
+                       dp1_header_ok(tv, th->md_len, th->md_off, md_blob_len, have_blob, v0_md);
+    const uint64_t tbl_id = th->bl_tx_id;
+    const bool a_branch = s < tbl_id;  // verification.go:191 vs :211
+    const uint8_t *sa = src_alh + 32 * p, *tba = o.tbl_alh + 32 * p;
+    w.alive[p] = alive;
+    w.ii[p] = s;
+    w.ij[p] = tbl_id;
+    w.ci[p] = sbl_id;
+    w.ls[p] = a_branch ? tbl_id : s;
+    copy32(w.x + 32 * p, sa);
+    copy32(w.x + 32 * (n + p), tgt_alh + 32 * p);
+    copy32(w.sbl + 32 * p, sh->bl_root);
+    copy32(w.tbl + 32 * p, th->bl_root);
+    copy32(w.lin_sa + 32 * p, a_branch ? tba : sa);
+    copy32(w.end_alh + 32 * p, a_branch ? sa : tba);
+    const uint64_t start = sbl_id, end = a_branch ? s : tbl_id;
+    uint8_t state;
+    if (end < start) state = 2;
+    else if (end <= start + 1) state = 1;
+    else if (!o.has_adv[p] || o.off[kAdv][p + 1] - o.off[kAdv][p] != end - start ||
+             o.off[kQ][p + 1] - o.off[kQ][p] != end - start - 1)
+        state = 2;
+    else state = 0;
+    w.a_state[p] = state;
+    w.a_start[p] = start;
+    w.a_cnt[p] = state == 0 ? end - start - 1 : 0;
+    static_assert(sizeof(mh_tx_header) % 8 == 0, "headers are copied in 8-byte words");
+    const uint2 *hs = (const uint2 *)sh, *ht = (const uint2 *)th;
+    uint2 *ds = (uint2 *)(w.hh + p), *dd = (uint2 *)(w.hh + n + p);
 #pragma unroll
-    for (int j = 0; j < 8; j++) d |= c[j] ^ x[j];
-    ok[p] = d == 0;
+    for (uint32_t i = 0; i < sizeof(mh_tx_header) / 8; i++) {
+        ds[i] = hs[i];
+        dd[i] = ht[i];
+    }
+    if (!alive) w.hh[p].version = w.hh[n + p].version = 1;
+    if (!alive || sv == 0) w.hh[p].md_len = 0;
+    if (!alive || tv == 0) w.hh[n + p].md_len = 0;
+}
+
+// Operands of the nested InclusionProofs (verification.go:108-115), one lane
+// per proof: lane q is nested proof first[0] + q, and its proof p is the one
+// with first[p] <= first[0] + q < first[p + 1].  The q of a proof whose chain
+// is not run gets i = j = 0, which the ahtree kernel rejects before it reads
+// a term.
+__global__ __launch_bounds__(256) void k_dp1_nested(uint64_t nq, uint64_t n,
+                                                    const uint64_t *__restrict__ first,
+                                                    const uint8_t *__restrict__ a_state,
+                                                    const uint64_t *__restrict__ a_start,
+                                                    const uint64_t *__restrict__ ij,
+                                                    const uint8_t *__restrict__ tbl,
+                                                    uint64_t *__restrict__ qi, uint64_t *__restrict__ qj,
+                                                    uint8_t *__restrict__ qroot) {
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    const uint64_t g = first[0] + q;
+    uint64_t lo = 0, hi = n;  // first[lo] <= g < first[hi] throughout
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (first[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    const bool run = a_state[lo] == 0;
+    qi[q] = run ? a_start[lo] + 1 + (g - first[lo]) : 0;
+    qj[q] = run ? ij[lo] : 0;
+    copy32(qroot + 32 * q, tbl + 32 * lo);
+}
+
+// The verdict in Go's order (verification.go:140-235), one proof per lane,
+// the AND over its nested proofs included.
+__global__ __launch_bounds__(256) void k_dp1_verdict(
+    uint64_t n, const uint8_t *__restrict__ alive, const int32_t *__restrict__ ast,
+    const uint64_t *__restrict__ ii, const uint64_t *__restrict__ ij, const uint64_t *__restrict__ ci,
+    const uint8_t *__restrict__ oki, const uint8_t *__restrict__ okc, const uint8_t *__restrict__ okl,
+    const uint8_t *__restrict__ has_lin, const uint8_t *__restrict__ oklin,
+    const uint8_t *__restrict__ a_state, const uint64_t *__restrict__ a_cnt,
+    const uint64_t *__restrict__ first, const uint8_t *__restrict__ aok,
+    const uint8_t *__restrict__ qok, uint8_t *__restrict__ ok) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    bool r = alive[p] && ast[p] == MH_OK && ast[n + p] == MH_OK;
+    if (r && ii[p] < ij[p]) r = oki[p];
+    if (r && ci[p] > 0) r = okc[p];
+    if (r && ij[p] > 0) r = okl[p];
+    if (r) r = has_lin[p] && oklin[p];
+    if (r) {
+        const uint8_t state = a_state[p];
+        if (state == 0) {
+            r = aok[p];
+            const uint64_t f = first[p] - first[0], c0 = a_cnt[p];
+            for (uint64_t x = 0; x < c0 && r; x++) r = qok[f + x];
+        } else {
+            r = state == 1;
+        }
+    }
+    ok[p] = r ? 1 : 0;
 }
 
 // Entry digest (tx.go:690-731) -- and, with leaf != 0, its htree leaf
@@ -805,17 +926,6 @@ hipError_t launch_linear_verify(hipStream_t st, Timer *tm, uint64_t n, const uin
     return hipGetLastError();
 }
 
-hipError_t launch_advance_chain(hipStream_t st, Timer *tm, uint64_t n, const uint64_t *start,
-                                const uint64_t *cnt, const uint64_t *term_off,
-                                const uint8_t *terms, const uint64_t *first,
-                                const uint8_t *end_alh, uint8_t *leaves_src, uint8_t *ok) {
-    if (!n) return hipSuccess;
-    TimerScope ts(tm, "advance_chain", st);
-    hipLaunchKernelGGL(k_advance_chain, dim3(grid_for(n, 256)), dim3(256), 0, st, n, start, cnt,
-                       term_off, terms, first, end_alh, leaves_src, ok);
-    return hipGetLastError();
-}
-
 hipError_t launch_advance_chain_gated(hipStream_t st, Timer *tm, uint64_t n, const uint8_t *state,
                                       const uint64_t *start, const uint64_t *cnt,
                                       const uint64_t *term_off, const uint8_t *terms,
@@ -825,6 +935,38 @@ hipError_t launch_advance_chain_gated(hipStream_t st, Timer *tm, uint64_t n, con
     TimerScope ts(tm, "advance_chain", st);
     hipLaunchKernelGGL(k_advance_chain_gated, dim3(grid_for(n, 256)), dim3(256), 0, st, n, state,
                        start, cnt, term_off, terms, first, end_alh, leaves_src, ok);
+    return hipGetLastError();
+}
+
+hipError_t launch_dp1_prep(hipStream_t st, Timer *tm, uint64_t n, const Dual1Arrays &o,
+                           const uint64_t *src, const uint64_t *tgt, const uint8_t *src_alh,
+                           const uint8_t *tgt_alh, const int32_t *status, uint64_t md_blob_len,
+                           Dp1V0Metadata v0_md, const Dp1Ops &w) {
+    if (!n) return hipSuccess;
+    TimerScope ts(tm, "dp1_prep", st);
+    hipLaunchKernelGGL(k_dp1_prep, dim3(grid_for(n, 256)), dim3(256), 0, st, n, o, src, tgt, src_alh,
+                       tgt_alh, status, md_blob_len, (int)v0_md, w);
+    return hipGetLastError();
+}
+
+hipError_t launch_dp1_nested(hipStream_t st, Timer *tm, uint64_t nq, uint64_t n,
+                             const uint64_t *first, const Dp1Ops &w, uint64_t *qi, uint64_t *qj,
+                             uint8_t *qroot) {
+    if (!nq) return hipSuccess;
+    TimerScope ts(tm, "dp1_nested", st);
+    hipLaunchKernelGGL(k_dp1_nested, dim3(grid_for(nq, 256)), dim3(256), 0, st, nq, n, first,
+                       w.a_state, w.a_start, w.ij, w.tbl, qi, qj, qroot);
+    return hipGetLastError();
+}
+
+hipError_t launch_dp1_verdict(hipStream_t st, Timer *tm, uint64_t n, const Dp1Ops &w,
+                              const Dp1Results &r, const uint8_t *has_lin, const uint64_t *first,
+                              uint8_t *ok) {
+    if (!n) return hipSuccess;
+    TimerScope ts(tm, "dp1_verdict", st);
+    hipLaunchKernelGGL(k_dp1_verdict, dim3(grid_for(n, 256)), dim3(256), 0, st, n, w.alive, r.ast,
+                       w.ii, w.ij, w.ci, r.oki, r.okc, r.okl, has_lin, r.oklin, w.a_state, w.a_cnt,
+                       first, r.aok, r.qok, ok);
     return hipGetLastError();
 }
 

@@ -500,7 +500,13 @@ int mh_verify_document_batch(mh_ctx *ctx, const mh_document_batch *batch, int32_
  * advance_incl_first[p] .. advance_incl_first[p+1]) whose terms are
  * advance_incl_terms[advance_incl_off[q] .. advance_incl_off[q+1]).
  * has_linear / has_advance = 0 stand for Go's nil proofs.  ok[p] = 1 iff the
- * proof verifies (the Go function returns bool). */
+ * proof verifies (the Go function returns bool); a header that cannot be
+ * hashed (version above 1, metadata on a version-0 header, metadata outside
+ * md_blob) makes it 0.  No offset array need start at 0 (a slice of a larger
+ * batch: advance the per-proof pointers, keep the term pointers); each must be
+ * monotonic, advance_incl_off over [advance_incl_first[0],
+ * advance_incl_first[n]], else MH_ERR_ILLEGAL_ARGUMENTS.  The arrays go up as
+ * they are and the whole check runs on the device. */
 typedef struct mh_dual_proof_batch {
     uint64_t n;
     const mh_tx_header *src_hdr;
@@ -948,10 +954,12 @@ int mh_verify_dual_proof_v2_pb_batch(mh_ctx *ctx, uint64_t n, const uint8_t *msg
  * message p: MH_OK, MH_ERR_CORRUPTED_DATA, or MH_ERR_ILLEGAL_ARGUMENTS (a
  * header or the linear proof missing).  ok[p] is 1 iff status[p] == MH_OK and
  * Go's VerifyDualProof(proof, src[p], tgt[p], src_alh[32 p], tgt_alh[32 p])
- * returns true on the decoded proof, i.e. mh_verify_dual_proof_batch's
- * verdict, except that a version-0 header's metadata is ignored, as Go's
- * innerHash ignores it (tx.go:258-263); a header version above 1 gives
- * ok = 0.  A message without LinearAdvanceProof is verified as Go verifies a
+ * returns true on the decoded proof.  Both this call and
+ * mh_verify_dual_proof_batch run one device verifier (dual_proof_v1_core,
+ * csrc/capi_tx.hip) and give one verdict, with a single difference: here a
+ * version-0 header's metadata is ignored, as Go's innerHash ignores it
+ * (tx.go:258-263), while the array call refuses such a header (ok = 0).  A
+ * header version above 1 gives ok = 0 in both.  A message without LinearAdvanceProof is verified as Go verifies a
  * nil one (true only where verification.go:90-97 needs none): nothing is
  * fetched, FillMissingLinearAdvanceProof is the caller's business.  n == 0
  * returns MH_OK; null pointers, a non-monotonic msg_off and n above the limits

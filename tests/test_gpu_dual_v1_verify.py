@@ -3,7 +3,11 @@ DualProof (v1) messages decoded and verified in one device pass
 (DualProofFromProto + store.VerifyDualProof, verification.go:127-235) against
 the C oracle, the CPU reference of dual_v1_verify_util.py and the composition
 of the two existing device calls (mh_dual_proof_pb_decode_batch, then
-mh_verify_dual_proof_batch)."""
+mh_verify_dual_proof_batch).  Both verify calls run dual_proof_v1_core; the
+last section drives the array call on its own (CSR bases, lane and grid edges,
+the header rules, its argument checks) and pins the one difference between the
+two: a v0 header that carries metadata."""
+import ctypes as C
 import os
 
 import numpy as np
@@ -323,3 +327,227 @@ def test_multi(devices, hostile):
         assert gst.size == 0 and gok.size == 0
     finally:
         md.close()
+
+
+# ------------------------------------------- 7. the array call, mh_verify_dual_proof_batch
+# bytes per proof of the per-proof arrays of mh_dual_proof_batch
+_PER_PROOF = {"src_hdr": 136, "tgt_hdr": 136, "incl_off": 8, "cons_off": 8, "target_bl_tx_alh": 32,
+              "last_off": 8, "has_linear": 1, "linear_src": 8, "linear_tgt": 8, "linear_off": 8,
+              "has_advance": 1, "advance_off": 8, "advance_incl_first": 8, "src": 8, "tgt": 8,
+              "src_alh": 32, "tgt_alh": 32}
+MH_MAX_TX_METADATA_LEN = 268
+
+
+def _arrays(args):
+    """orc.verify_dual_proof argument tuples -> the arrays of mh_dual_proof_batch
+    (all but md_blob), every offset array from 0"""
+    from immustore_amd.txlayer import _d32, _hdrs, _terms_csr
+    n = len(args)
+    a = {"src_hdr": _hdrs(np.array([x[0] for x in args])),
+         "tgt_hdr": _hdrs(np.array([x[1] for x in args]))}
+    for name, col in (("incl", 3), ("cons", 4), ("last", 6)):
+        a[name + "_off"], a[name + "_terms"] = _terms_csr([x[col] for x in args])
+    lin, adv = [x[7] for x in args], [x[8] for x in args]
+    a["has_linear"] = np.array([x is not None for x in lin], np.uint8)
+    a["linear_src"] = np.array([x[0] if x is not None else 0 for x in lin], np.uint64)
+    a["linear_tgt"] = np.array([x[1] if x is not None else 0 for x in lin], np.uint64)
+    a["linear_off"], a["linear_terms"] = _terms_csr([x[2] if x is not None else [] for x in lin])
+    a["has_advance"] = np.array([x is not None for x in adv], np.uint8)
+    a["advance_off"], a["advance_terms"] = _terms_csr([x[0] if x is not None else [] for x in adv])
+    nested = [x[1] if x is not None else [] for x in adv]
+    a["advance_incl_first"] = np.zeros(n + 1, np.uint64)
+    a["advance_incl_first"][1:] = np.cumsum([len(x) for x in nested], dtype=np.uint64)
+    a["advance_incl_off"], a["advance_incl_terms"] = _terms_csr([ip for ns in nested for ip in ns])
+    a["target_bl_tx_alh"] = _d32([x[5] for x in args], n)
+    a["src"] = np.array([x[9] for x in args], np.uint64)
+    a["tgt"] = np.array([x[10] for x in args], np.uint64)
+    a["src_alh"], a["tgt_alh"] = _d32([x[11] for x in args], n), _d32([x[12] for x in args], n)
+    return a
+
+
+def _call(ctx, a, lo=0, n=None, md_blob=None, md_blob_len=None):
+    """mh_verify_dual_proof_batch over proofs [lo, lo + n) of the arrays: every
+    per-proof pointer advanced by lo, the term pointers at the arrays' start
+    -> (return code, ok[n], 7 where the call wrote nothing)"""
+    from immustore_amd import _native as N
+    from immustore_amd.txlayer import _DualProofBatch, _addr
+    n = a["src"].size - lo if n is None else n
+    kw = {name: _addr(a[name]) + lo * _PER_PROOF.get(name, 0)
+          for name, _ in _DualProofBatch._fields_ if name not in ("n", "md_blob", "md_blob_len")}
+    if md_blob_len is None:
+        md_blob_len = 0 if md_blob is None else md_blob.size
+    b = _DualProofBatch(n=n, md_blob=_addr(md_blob), md_blob_len=md_blob_len, **kw)
+    ok = np.full(n, 7, np.uint8)
+    rc = N.load().mh_verify_dual_proof_batch(ctx.handle, C.byref(b), _addr(ok))
+    return rc, ok
+
+
+@pytest.fixture(scope="module")
+def mixed(orc, fixtures):
+    """the 478 dual_v1 cases of the Go stores, case k with tamper k % 5 of
+    (none, lap, lin, last, tbl) -> (arguments, oracle verdicts, arrays)"""
+    from test_tx_oracle import dual_v1_args
+    from tx_util import headers_from_fixture
+    args = []
+    for name, fx in fixtures.items():
+        recs, blob, alhs = headers_from_fixture(fx["txs"])
+        assert blob == b""
+        for c in fx["dual_v1"]:
+            tamper = (None, "lap", "lin", "last", "tbl")[len(args) % 5]
+            args.append(dual_v1_args(c, recs, blob, alhs, tamper))
+    assert len(args) == 478
+    return args, [orc.verify_dual_proof(*x) for x in args], _arrays(args)
+
+
+def _span(x):
+    """(start, end) of the linear advance proof of an argument tuple
+    (verification.go:191-233)"""
+    s, sbl, tbl = int(x[9]), int(x[0]["bl_tx_id"]), int(x[1]["bl_tx_id"])
+    return sbl, (s if s < tbl else tbl)
+
+
+def test_arrays_nonzero_csr_bases(ctx, mixed):
+    """100 proofs from case 300 on (the first 284 cases carry no advance terms,
+    a window at 200 would start two of the arrays at 0): every offset array
+    starts above 0 while the term pointers stay at the arrays' start."""
+    args, exp, a = mixed
+    lo, n = 300, 100
+    first = a["advance_incl_first"]
+    for name in ("incl_off", "cons_off", "last_off", "linear_off", "advance_off",
+                 "advance_incl_first"):
+        assert a[name][lo] != 0, name
+    assert a["advance_incl_off"][int(first[lo])] != 0
+    assert first[lo + n] > first[lo]  # nested inclusion proofs inside the window
+    assert any(exp[lo:lo + n]) and not all(exp[lo:lo + n])
+    rc, ok = _call(ctx, a, lo, n)
+    assert rc == 0
+    assert [bool(x) for x in ok] == exp[lo:lo + n]
+
+
+@pytest.mark.parametrize("n", [1, 256, 257])
+def test_arrays_lane_and_grid_edges(ctx, mixed, n):
+    args, exp, _ = mixed
+    pick = [(285 + 3 * k) % len(args) for k in range(n)]
+    # n = 1: a proof that verifies through its nested inclusion proofs
+    assert exp[pick[0]] and args[pick[0]][8] is not None and any(args[pick[0]][8][1])
+    rc, ok = _call(ctx, _arrays([args[k] for k in pick]))
+    assert rc == 0
+    assert [bool(x) for x in ok] == [exp[k] for k in pick]
+
+
+def test_arrays_no_nested_proofs(ctx, mixed):
+    """Q = 0: no proof's chain runs (end <= start + 1 everywhere), the nested
+    launches are skipped."""
+    args, exp, _ = mixed
+    pick = [k for k, x in enumerate(args)
+            if _span(x)[1] <= _span(x)[0] + 1 and not (x[8] and x[8][1])][:70]
+    assert len(pick) >= 20
+    a = _arrays([args[k] for k in pick])
+    assert a["advance_incl_first"][len(pick)] == 0
+    rc, ok = _call(ctx, a)
+    assert rc == 0
+    assert [bool(x) for x in ok] == [exp[k] for k in pick]
+    assert any(exp[k] for k in pick) and not all(exp[k] for k in pick)
+
+
+def test_arrays_header_rules_on_device(ctx, mixed):
+    """One proof that verifies, one thing changed at a time: false, the call
+    itself MH_OK, and the neighbours keep their verdicts."""
+    args, exp, _ = mixed
+    v = next(k for k, x in enumerate(args)
+             if exp[k] and _span(x)[1] > _span(x)[0] + 2 and x[8] and len(x[8][1]) >= 2)
+    pick = [v - 2, v - 1, v, v + 1, v + 2]
+    want = [exp[k] for k in pick]
+    blob = np.arange(64, dtype=np.uint8)
+
+    def run(change=None, swap=None, **kw):
+        batch = [args[k] for k in pick]
+        if swap:
+            batch[2] = batch[2][:8] + (swap(batch[2][8]),) + batch[2][9:]
+        a = _arrays(batch)
+        if change:
+            change(a)
+        rc, ok = _call(ctx, a, **kw)
+        assert rc == 0
+        return [bool(x) for x in ok]
+
+    assert run(md_blob=blob) == want and want[2]
+
+    def hdr(which, **fields):
+        def change(a):
+            for f, val in fields.items():
+                a[which][f][2] = val
+        return change
+
+    def flag(name):
+        def change(a):
+            a[name][2] = 0
+        return change
+
+    variants = {
+        "v0 source header with metadata": dict(change=hdr("src_hdr", version=0, md_len=5), md_blob=blob),
+        "target header version 2": dict(change=hdr("tgt_hdr", version=2), md_blob=blob),
+        "metadata past the blob": dict(change=hdr("src_hdr", version=1, md_len=4, md_off=blob.size - 3),
+                                       md_blob=blob),
+        "metadata without a blob": dict(change=hdr("tgt_hdr", version=1, md_len=4, md_off=0)),
+        "metadata too long": dict(change=hdr("src_hdr", version=1, md_len=MH_MAX_TX_METADATA_LEN + 1,
+                                             md_off=0),
+                                  md_blob=np.zeros(512, np.uint8)),
+        "no advance proof": dict(change=flag("has_advance"), md_blob=blob),
+        "advance terms one short": dict(swap=lambda lap: (lap[0][:-1], lap[1]), md_blob=blob),
+        "nested proofs one short": dict(swap=lambda lap: (lap[0], lap[1][:-1]), md_blob=blob),
+        "no linear proof": dict(change=flag("has_linear"), md_blob=blob),
+    }
+    for name, kw in variants.items():
+        assert run(**kw) == want[:2] + [False] + want[3:], name
+
+
+def test_arrays_nested_offsets_checked(ctx, mixed):
+    """advance_incl_off running backwards inside [first[0], first[n]] is
+    refused before anything is launched; outside that window it is not read."""
+    args, exp, a = mixed
+    lo, n = 300, 100
+    q0, q1 = int(a["advance_incl_first"][lo]), int(a["advance_incl_first"][lo + n])
+    off = a["advance_incl_off"]
+    assert q0 >= 1 and q1 + 1 < off.size
+    k = next(q for q in range(q0, q1) if off[q + 1] > off[q])
+    bad = dict(a, advance_incl_off=off.copy())
+    bad["advance_incl_off"][[k, k + 1]] = off[[k + 1, k]]
+    rc, ok = _call(ctx, bad, lo, n)
+    assert rc == 2 and (ok == 7).all()
+    outside = dict(a, advance_incl_off=off.copy())
+    outside["advance_incl_off"][0] = 1 << 40  # above entry 1
+    outside["advance_incl_off"][-1] = 0       # below the entry before it
+    rc, ok = _call(ctx, outside, lo, n)
+    assert rc == 0
+    assert [bool(x) for x in ok] == exp[lo:lo + n]
+
+
+def test_v0_metadata_wire_drops_arrays_refuse(ctx, orc, wire, mixed):
+    """The one intended difference between the two callers of the verifier: a
+    v0 source header that carries metadata on the wire.  The fused call drops
+    the metadata as Go's innerHash does (tx.go:258-263): the CPU reference's
+    verdict.  The array call on the decoded arrays keeps check_header's rule:
+    false.  (_compose above zeroes md_len of decoded v0 headers before the
+    array call, which is why the composition test sees no difference.)"""
+    from dual_v1_verify_util import reference
+    from immustore_amd import txlayer
+    from test_gpu_pb_decode import dual_v1_msg
+    args, exp, _ = mixed
+    pick = [k for k, x in enumerate(args) if exp[k] and int(x[0]["version"]) == 0][:3]
+    assert len(pick) == 3
+    msgs = [dual_v1_msg(wire, args[k]) for k in pick]
+    M = wire.MSG["DualProof"].FromString(msgs[1])
+    M.sourceTxHeader.metadata.truncatedTxID = 5
+    msgs[1] = M.SerializeToString()
+    S, T = [args[k][9] for k in pick], [args[k][10] for k in pick]
+    SA, TA = [args[k][11] for k in pick], [args[k][12] for k in pick]
+    ref = [reference(wire, orc, msgs[k], S[k], T[k], SA[k], TA[k]) for k in range(3)]
+    assert ref == [(0, True)] * 3
+    st, ok = txlayer.verify_dual_proof_pb_batch(msgs, S, T, SA, TA, ctx=ctx)
+    assert [(int(a), bool(b)) for a, b in zip(st, ok)] == ref
+    st, dec = txlayer.decode_dual_proof_pb(msgs, ctx=ctx)
+    assert (st == 0).all()
+    assert dec["src_hdr"]["version"][1] == 0 and dec["src_hdr"]["md_len"][1] == 9
+    ok = txlayer.verify_decoded_dual_proof_batch(dec, S, T, SA, TA, ctx=ctx)
+    assert list(ok) == [True, False, True]
