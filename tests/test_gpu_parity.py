@@ -46,6 +46,19 @@ def lpl(request):
         os.environ["MH_LPL"] = old
 
 
+@pytest.fixture(params=["1", "2", "4"])
+def digest_lpl(request):
+    """Digests per lane of k_leaves_from_digests (HTree.build_with and
+    mh_dev_htree_build_digests read MH_DIGEST_LPL, not MH_LPL)."""
+    old = os.environ.get("MH_DIGEST_LPL")
+    os.environ["MH_DIGEST_LPL"] = request.param
+    yield int(request.param)
+    if old is None:
+        del os.environ["MH_DIGEST_LPL"]
+    else:
+        os.environ["MH_DIGEST_LPL"] = old
+
+
 # ------------------------------------------------------------------ SHA-256
 def test_sha256_batch_any_alignment(m, ctx):
     from immustore_amd import _native as N
@@ -79,9 +92,11 @@ def test_sha256_batch_any_alignment(m, ctx):
 
 
 def test_sha256_batch_ragged_length_classes(m, ctx):
-    """Many ragged messages (the length-class sorted kernel, n > 256): every
-    length 0..1100 several times over at random alignments, a spread up to
-    4 KiB, and messages past the last length class (> 1023 blocks)."""
+    """9309 ragged messages, below the 16384 from which the length-class sort
+    runs, so k_sha_varlen in input order (the sorted kernel is covered in
+    test_gpu_dispatch_arms.py): every length 0..1100 several times over at
+    random alignments, a spread up to 4 KiB, and messages past the last length
+    class (> 1023 blocks)."""
     from immustore_amd import _native as N
     rng = np.random.default_rng(12)
     lens = np.concatenate([np.tile(np.arange(0, 1101), 3), rng.integers(0, 4097, 6000),
@@ -148,7 +163,7 @@ def test_entries_ragged_with_overrides_vs_oracle(m, ctx, orc):
 
 
 # ------------------------------------------------------------------ htree
-def test_htree_build_with_golden(m, ctx, synthetic, lpl):
+def test_htree_build_with_golden(m, ctx, synthetic, digest_lpl):
     for case in synthetic["htree"]:
         w = case["width"]
         digs = [H(struct.pack(">Q", i)) for i in range(w)]
@@ -190,7 +205,7 @@ def test_htree_errors(m, ctx):
         t.inclusion_proof(1000)
 
 
-def test_htree_random_widths_vs_oracle(m, ctx, orc, lpl):
+def test_htree_random_widths_vs_oracle(m, ctx, orc, digest_lpl):
     rng = np.random.default_rng(5)
     for w in [1, 2, 3, 4, 5, 6, 7, 8, 9, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025,
               4095, 4097, 65535, 65537, 262145, 1048577]:

@@ -79,14 +79,17 @@ def test_htree_build_many_vs_oracle(m, ctx, orc):
     roots = m.htree_build_many(trees, ctx)
     for t, r in zip(trees, roots):
         assert r.tobytes() == orc.htree_build(t)[1]
-    # every width <= 64: the one-lane-per-tree kernel instead of the host plan
-    small = [t for t in trees if len(t) <= 64] + [rng.integers(0, 256, (64, 32), dtype=np.uint8)]
+    # every width <= 64 (small_roots_fit): launch_small_roots instead of the
+    # host tree plan; up to 2048 trees, so a wave per tree (k_small_roots_wave)
+    small =[t for t in trees if len(t) <= 64] + [rng.integers(0, 256, (64, 32), dtype=np.uint8)]
     roots = m.htree_build_many(small, ctx)
     for t, r in zip(small, roots):
         assert r.tobytes() == orc.htree_build(t)[1]
-    # every shape class of the many-tree dispatch (small_roots_fit): few trees
-    # up to 64 wide (a wave per tree), many trees up to 16 wide (a lane per
-    # tree), many trees of 17..64 (level-parallel through the plan)
+    # the many-tree dispatch of launch_small_roots (widest tree <= 64): up to
+    # 2048 trees a wave per tree (k_small_roots_wave), more than 2048 the
+    # level-parallel packed kernel (k_small_roots_pack) with
+    # lgp = ceil(log2(widest)) -- 4 for widths 1..16, 6 for 17..64 and 60..64
+    # (the other lgp values run in test_gpu_dispatch_arms.py)
     for count, lo, hi in ((2048, 1, 65), (3000, 1, 17), (3000, 17, 65), (2049, 60, 65)):
         ts = [rng.integers(0, 256, (int(w), 32), dtype=np.uint8)
               for w in rng.integers(lo, hi, count)]
