@@ -525,6 +525,12 @@ def ahtree_verify_last_inclusion(iproof, i, leaf, root, ctx=None) -> bool:
     return bool(_aht_batch(N.MH_AHT_LAST_INCLUSION, [(iproof, i, i, leaf, root)], ctx)[0][0])
 
 
+def ahtree_eval_last_inclusion(iproof, i, leaf, ctx=None) -> bytes:
+    """ahtree/verification.go:119-137."""
+    _, ev = _aht_batch(N.MH_AHT_LAST_INCLUSION, [(iproof, i, i, leaf, b"\0" * 32)], ctx, True)
+    return ev[0].tobytes()
+
+
 def ahtree_verify_batch(kind, items, ctx=None, want_eval=False):
     return _aht_batch(kind, items, ctx, want_eval)
 

@@ -383,7 +383,13 @@ int mh_dev_ahtree_peaks(mh_ctx *ctx, const uint8_t *dlog, uint64_t n, uint8_t *p
  * CONSISTENCY:    a = root of i, b = root of j
  * LAST_INCLUSION: a = leaf, b = root (j ignored)
  * ok[p] = Verify*(...) ; eval_out (np*32 for INCLUSION / LAST, np*64 for
- * CONSISTENCY = ci||cj) may be NULL. */
+ * CONSISTENCY = ci||cj) may be NULL.  eval_out[p] is Go's EvalInclusion /
+ * EvalConsistency / EvalLastInclusion of the proof wherever the verifier
+ * walks it.  Where it answers without a walk -- i > j, i == 0, or i < j with
+ * no terms (verification.go:22-24, :59-61), and for CONSISTENCY also i == j
+ * with no terms (:63-65, where Go's Eval would index an empty proof) --
+ * eval_out[p] is the leaf a[p] unchanged for INCLUSION and 64 zero bytes for
+ * CONSISTENCY.  LAST_INCLUSION always walks, i == 0 included (ok[p] = 0). */
 int mh_ahtree_verify_batch(mh_ctx *ctx, int kind, uint64_t nproofs, const uint64_t *i,
                            const uint64_t *j, const uint64_t *term_off, const uint8_t *terms,
                            const uint8_t *a, const uint8_t *b, uint8_t *ok, uint8_t *eval_out);

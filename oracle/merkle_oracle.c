@@ -900,6 +900,70 @@ uint64_t orc_ahtree_verify_batch(int kind, uint64_t n, const uint64_t *i, const 
     return cnt;
 }
 
+/* Go's EvalInclusion / EvalConsistency / EvalLastInclusion (kind 0/1/2) of
+ * every proof of a CSR batch: out[p] is 32 bytes (kind 0 / 2, from leaf a[p])
+ * or 64 bytes ciRoot || cjRoot (kind 1, a unused).  defined[p] = 0 and out[p]
+ * untouched where Go would panic (EvalConsistency of an empty proof). */
+void orc_ahtree_eval_batch(int kind, uint64_t n, const uint64_t *i, const uint64_t *j,
+                           const uint64_t *term_off, const uint8_t *terms, const uint8_t *a,
+                           uint8_t *out, uint8_t *defined) {
+    for (uint64_t p = 0; p < n; p++) {
+        const uint8_t *t = terms + term_off[p] * 32;
+        const uint32_t nt = (uint32_t)(term_off[p + 1] - term_off[p]);
+        defined[p] = 1;
+        if (kind == 0)
+            orc_ahtree_eval_inclusion(t, nt, i[p], j[p], a + 32 * p, out + 32 * p);
+        else if (kind == 2)
+            orc_ahtree_eval_last_inclusion(t, nt, i[p], a + 32 * p, out + 32 * p);
+        else if (orc_ahtree_eval_consistency(t, nt, i[p], j[p], out + 64 * p, out + 64 * p + 32))
+            defined[p] = 0;
+    }
+}
+
+/* orc_htree_verify_batch over CSR term lists with a width and a root per
+ * proof, split over nthreads host threads. */
+typedef struct {
+    uint64_t lo, hi;
+    const uint64_t *leaf, *width, *term_off;
+    const uint8_t *terms, *digests, *roots;
+    uint8_t *ok;
+    uint64_t cnt;
+} ht_vjob;
+
+static void *ht_verify_worker(void *arg) {
+    ht_vjob *J = (ht_vjob *)arg;
+    for (uint64_t p = J->lo; p < J->hi; p++) {
+        const int r = orc_htree_verify_inclusion(
+            J->leaf[p], J->width[p], J->terms + J->term_off[p] * 32,
+            (uint32_t)(J->term_off[p + 1] - J->term_off[p]), J->digests + 32 * p, J->roots + 32 * p);
+        J->ok[p] = (uint8_t)r;
+        J->cnt += (uint64_t)r;
+    }
+    return NULL;
+}
+
+uint64_t orc_htree_verify_csr(uint64_t n, const uint64_t *leaf, const uint64_t *width,
+                              const uint64_t *term_off, const uint8_t *terms,
+                              const uint8_t *digests, const uint8_t *roots, uint8_t *ok,
+                              int nthreads) {
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 64) nthreads = 64;
+    ht_vjob jobs[64];
+    pthread_t th[64];
+    for (int t = 0; t < nthreads; t++) {
+        ht_vjob J = {n * t / nthreads, n * (t + 1) / nthreads, leaf, width, term_off, terms,
+                     digests, roots, ok, 0};
+        jobs[t] = J;
+        pthread_create(&th[t], NULL, ht_verify_worker, &jobs[t]);
+    }
+    uint64_t cnt = 0;
+    for (int t = 0; t < nthreads; t++) {
+        pthread_join(th[t], NULL);
+        cnt += jobs[t].cnt;
+    }
+    return cnt;
+}
+
 /* ------------------------------------------------ streamed ahtree (checker) */
 static uint64_t splitmix_word(uint64_t seed, uint64_t w) {
     /* word w of orc_fill_random(seed): splitmix64 output number w+1 */

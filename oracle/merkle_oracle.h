@@ -63,6 +63,21 @@ uint64_t orc_ahtree_verify_batch(int kind, uint64_t n, const uint64_t *i, const 
                                  const uint64_t *term_off, const uint8_t *terms, const uint8_t *a,
                                  const uint8_t *b, uint8_t *ok, int nthreads);
 
+/* Go's Eval{Inclusion,Consistency,LastInclusion} (kind 0/1/2) of every proof
+ * of such a batch: out[p] = 32 bytes (kind 0 / 2, from the leaf a[p]) or 64
+ * bytes ciRoot || cjRoot (kind 1); defined[p] = 0, out[p] untouched, where Go
+ * would panic (EvalConsistency of an empty proof). */
+void orc_ahtree_eval_batch(int kind, uint64_t n, const uint64_t *i, const uint64_t *j,
+                           const uint64_t *term_off, const uint8_t *terms, const uint8_t *a,
+                           uint8_t *out, uint8_t *defined);
+
+/* orc_htree_verify_batch over CSR term lists, a width and a root per proof,
+ * nthreads host threads. */
+uint64_t orc_htree_verify_csr(uint64_t n, const uint64_t *leaf, const uint64_t *width,
+                              const uint64_t *term_off, const uint8_t *terms,
+                              const uint8_t *digests, const uint8_t *roots, uint8_t *ok,
+                              int nthreads);
+
 /* Value hash loop (embedded/store/immustore.go:1620-1630) + Tx.BuildHashTree
  * (embedded/store/tx.go:332-355): CSR inputs (offsets have n+1 entries).
  * md / md_off may be NULL (no KV metadata).  hval_override / use_override

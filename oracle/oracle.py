@@ -77,6 +77,12 @@ def lib():
         L.orc_ahtree_verify_batch.restype = C.c_uint64
         L.orc_ahtree_verify_batch.argtypes = [C.c_int, C.c_uint64, u64p, u64p, u64p, u8p, u8p,
                                               u8p, u8p, C.c_int]
+        L.orc_ahtree_eval_batch.restype = None
+        L.orc_ahtree_eval_batch.argtypes = [C.c_int, C.c_uint64, u64p, u64p, u64p, u8p, u8p, u8p,
+                                            u8p]
+        L.orc_htree_verify_csr.restype = C.c_uint64
+        L.orc_htree_verify_csr.argtypes = [C.c_uint64, u64p, u64p, u64p, u8p, u8p, u8p, u8p,
+                                           C.c_int]
         L.orc_verify_linear_proof.argtypes = [C.c_uint64, C.c_uint64, u8p, C.c_uint32, C.c_uint64,
                                               C.c_uint64, u8p, u8p]
         L.orc_verify_linear_advance_proof.argtypes = [C.c_int, u8p, C.c_uint32, u8p, u32p,
@@ -367,6 +373,51 @@ def ahtree_eval_consistency(proof, i, j):
 def ahtree_verify_last_inclusion(proof, i, leaf, root):
     tp, nt = _terms(proof)
     return bool(lib().orc_ahtree_verify_last_inclusion(tp, nt, i, _p(_u8(leaf)), _p(_u8(root))))
+
+
+def ahtree_eval_last_inclusion(proof, i, leaf):
+    tp, nt = _terms(proof)
+    out = np.zeros(32, np.uint8)
+    lib().orc_ahtree_eval_last_inclusion(tp, nt, i, _p(_u8(leaf)), _p(out))
+    return out.tobytes()
+
+
+def ahtree_eval_batch(kind, i, j, term_off, terms, a):
+    """Go's EvalInclusion / EvalConsistency / EvalLastInclusion (kind 0/1/2)
+    over CSR proofs as for ahtree_verify_batch -> (out (n, 32) or (n, 64) =
+    ciRoot || cjRoot, defined[n]: False where Go would panic, an empty
+    consistency proof; out is zero there)."""
+    iv = np.ascontiguousarray(i, np.uint64)
+    jv = np.ascontiguousarray(j, np.uint64)
+    to = np.ascontiguousarray(term_off, np.uint64)
+    t = np.ascontiguousarray(terms, np.uint8).reshape(-1, 32)
+    if t.shape[0] == 0:
+        t = np.zeros((1, 32), np.uint8)
+    av = np.ascontiguousarray(a, np.uint8)
+    n = iv.shape[0]
+    out = np.zeros((max(n, 1), 64 if kind == 1 else 32), np.uint8)
+    ok = np.zeros(max(n, 1), np.uint8)
+    lib().orc_ahtree_eval_batch(kind, n, _p(iv, u64p), _p(jv, u64p), _p(to, u64p), _p(t), _p(av),
+                                _p(out), _p(ok))
+    return out[:n], ok[:n].astype(bool)
+
+
+def htree_verify_csr(leaf, width, term_off, terms, digests, roots, nthreads=1):
+    """htree.VerifyInclusion over CSR proofs with a width and a root per
+    proof (leaf / width: the bits of Go ints).  Returns (count verified, ok[n])."""
+    lf = np.ascontiguousarray(leaf, np.uint64)
+    wd = np.ascontiguousarray(width, np.uint64)
+    to = np.ascontiguousarray(term_off, np.uint64)
+    t = np.ascontiguousarray(terms, np.uint8).reshape(-1, 32)
+    if t.shape[0] == 0:
+        t = np.zeros((1, 32), np.uint8)
+    d = np.ascontiguousarray(digests, np.uint8)
+    r = np.ascontiguousarray(roots, np.uint8)
+    n = lf.shape[0]
+    ok = np.zeros(max(n, 1), np.uint8)
+    c = lib().orc_htree_verify_csr(n, _p(lf, u64p), _p(wd, u64p), _p(to, u64p), _p(t), _p(d),
+                                   _p(r), _p(ok), nthreads)
+    return c, ok[:n]
 
 
 def verify_values(vals, off, hvals, vlen=None, nthreads=1):

@@ -379,20 +379,7 @@ def test_decode_capacity_and_arguments(m, ctx, wire):
 
 
 # ------------------------------------------------------------ InclusionProof
-def go_verify_inclusion(leaf, width, terms, digest, root):
-    """htree.VerifyInclusion (htree.go:166-195) with Go's int arithmetic
-    (truncating / and %), in Python: the checker for negative leaf / width."""
-    import hashlib
-    calc = hashlib.sha256(b"\0" + digest).digest()
-    i, r = leaf, width - 1
-    tdiv = lambda x: -((-x) // 2) if x < 0 else x // 2  # noqa: E731
-    for t in terms:
-        if i % 2 == 0 and i != r:
-            calc = hashlib.sha256(b"\1" + calc + t).digest()
-        else:
-            calc = hashlib.sha256(b"\1" + t + calc).digest()
-        i, r = tdiv(i), tdiv(r)
-    return i == r and calc == root
+from verify_mutants_util import go_verify_inclusion  # noqa: E402  (htree.go:166-195 in Python)
 
 
 def random_incl_msg(wire, rng):
