@@ -146,14 +146,7 @@ __global__ __launch_bounds__(256) void k_doc_state(
         if (s == MH_OK && srcid == 0) s = MH_ERR_ILLEGAL_ARGUMENTS;
     }
     status[d] = s;
-    ii[d] = srcid;  // :342-348
-    ij[d] = th.bl_tx_id;
-    sel[d] = srcid == 1;  // :354-370
-    ci[d] = srcid == 1 ? srcid : sh.bl_tx_id;
-    for (int k = 0; k < 32; k++) {
-        sbl[32 * d + k] = sh.bl_root[k];
-        tbl[32 * d + k] = th.bl_root[k];
-    }
+    dpv2_operands(d, srcid, &sh, &th, ii, ij, ci, sel, sbl, tbl);  // :342-370
 }
 
 // The rest of VerifyDualProofV2 (:328-370) and the new state's Alh.
@@ -167,16 +160,7 @@ __global__ __launch_bounds__(256) void k_doc_final(uint64_t n, const mh_tx_heade
     if (d >= n) return;
     const mh_tx_header &sh = h3[n + d], &th = h3[2 * n + d];
     int32_t s = status[d];
-    if (s == MH_OK) {
-        if (sh.id - 1 != sh.bl_tx_id || th.id - 1 != th.bl_tx_id)
-            s = MH_ERR_UNEXPECTED_LINKING;  // :328-330
-        else if (sh.id == th.id)
-            s = MH_OK;  // :332-334
-        else if (!oki[d])
-            s = MH_ERR_INCLUSION_NOT_VALID;
-        else if (!okc[d])
-            s = MH_ERR_CONSISTENCY_NOT_VALID;
-    }
+    if (s == MH_OK) s = dpv2_ladder(&sh, &th, sh.id == th.id, oki[d], okc[d]);
     status[d] = s;
     const uint8_t *talh = alh3 + 32 * (2 * n + d);
     for (int k = 0; k < 32; k++) talh_out[32 * d + k] = s == MH_OK ? talh[k] : 0;
@@ -406,16 +390,12 @@ extern "C" int mh_verify_document_batch(mh_ctx *c, const mh_document_batch *B, i
         // 5. leafFor(sourceAlh) (verification.go:346) and the two ahtree proofs
         //    for every document (a document already failed keeps its status);
         //    the caller's term offsets, the terms' base shifted by the first
-        MH_HIP(launch_leaf_for(st, c->tm(), n, base + b_alh + 32 * n, base + b_leaf));
-        MH_HIP(launch_ahtree_verify(st, c->tm(), MH_AHT_INCLUSION, n, (const uint64_t *)(base + b_ii),
-                                    (const uint64_t *)(base + b_ij), (const uint64_t *)dp(b_io),
-                                    dp(b_it) - 32 * i0, base + b_leaf, base + b_tbl,
-                                    base + b_oki, nullptr));
-        MH_HIP(launch_select32(st, n, base + b_sel, base + b_leaf, base + b_sbl, base + b_ca));
-        MH_HIP(launch_ahtree_verify(st, c->tm(), MH_AHT_CONSISTENCY, n,
-                                    (const uint64_t *)(base + b_ci), (const uint64_t *)(base + b_ij),
-                                    (const uint64_t *)dp(b_co), dp(b_ct) - 32 * c0,
-                                    base + b_ca, base + b_tbl, base + b_okc, nullptr));
+        MH_HIP(launch_dpv2_proofs(st, c->tm(), n, (const uint64_t *)(base + b_ii),
+                                  (const uint64_t *)(base + b_ij), (const uint64_t *)(base + b_ci),
+                                  base + b_sel, base + b_sbl, base + b_tbl, base + b_alh + 32 * n,
+                                  (const uint64_t *)dp(b_io), dp(b_it) - 32 * i0,
+                                  (const uint64_t *)dp(b_co), dp(b_ct) - 32 * c0, base + b_leaf,
+                                  base + b_ca, base + b_oki, base + b_okc));
         hipLaunchKernelGGL(k_doc_final, dim3(g1), dim3(256), 0, st, n, h3, base + b_alh,
                            base + b_oki, base + b_okc, (int32_t *)(base + b_st), base + b_ta);
         MH_HIP(hipGetLastError());

@@ -644,14 +644,20 @@ inline uint64_t plan_index_bytes(const TreePlan &P, uint64_t ntrees) {
 // innerHash / Alh of checked headers (capi_tx.hip); c->mu held by the caller.
 int tx_alh_core(mh_ctx *c, uint64_t n, const mh_tx_header *hdrs, const uint8_t *md_blob,
                 uint64_t md_blob_len, uint8_t *inner_out, uint8_t *alh_out);
-// VerifyDualProofV2 over checked arguments (capi_tx.hip); alh_checked skips
-// the header Alh pass when the caller has matched them already; c->mu held.
-int dual_proof_v2_core(mh_ctx *c, uint64_t n, const mh_tx_header *sh, const mh_tx_header *th,
-                       const uint8_t *md_blob, uint64_t md_blob_len, const uint64_t *incl_off,
-                       const uint8_t *incl_terms, const uint64_t *cons_off,
-                       const uint8_t *cons_terms, const uint64_t *src, const uint64_t *tgt,
-                       const uint8_t *src_alh, const uint8_t *tgt_alh, int32_t *status,
-                       bool alh_checked);
+// VerifyDualProofV2 (verification.go:303-372) over n proofs on the device
+// (capi_tx.hip): THE statement of the V2 verifier, behind the array call and
+// the wire call, as dual_proof_v1_core below is for v1.  Every array device
+// memory, n entries; offsets and biased term pointers as in Dual1Arrays;
+// status_in nullable, or status_out itself: a proof not MH_OK there keeps its
+// status; scratch: dual_proof_v2_scratch_bytes(n), 256-byte aligned.
+uint64_t dual_proof_v2_scratch_bytes(uint64_t n);
+int dual_proof_v2_core(hipStream_t st, Timer *tm, uint64_t n, const mh_tx_header *src_hdr,
+                       const mh_tx_header *tgt_hdr, const uint8_t *md_blob,
+                       const uint64_t *incl_off, const uint8_t *incl_terms,
+                       const uint64_t *cons_off, const uint8_t *cons_terms, const uint64_t *src,
+                       const uint64_t *tgt, const uint8_t *src_alh, const uint8_t *tgt_alh,
+                       const int32_t *status_in, uint64_t md_blob_len, Dp1V0Metadata v0_md,
+                       uint8_t *scratch, int32_t *status_out);
 // VerifyDualProof (v1, verification.go:127-235) over nk decoded proofs that
 // are on the device already (capi_tx.hip): THE statement of the v1 verifier,
 // behind both mh_verify_dual_proof_batch (the caller's arrays, uploaded) and

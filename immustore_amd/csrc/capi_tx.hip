@@ -229,114 +229,59 @@ extern "C" int mh_verify_linear_proof_batch(mh_ctx *c, uint64_t n, const uint64_
     });
 }
 
-// VerifyDualProofV2 (verification.go:305-372) over n proofs whose arguments
-// have been checked (offsets monotonic, term arrays present).  The host-built
-// arrays are written straight into one pinned staging area laid out like
-// their device copies and go up in ONE copy; the results come back the same
-// way.  alh_checked: the caller has already matched both headers' Alh with
-// src_alh / tgt_alh and rejected unhashable headers (the VerifyDocument batch,
-// which hashes every header once) -- the Alh pass (:318-326) is skipped.
-// c->mu held by the caller (c->p_stage, c->s_tx).
-int dual_proof_v2_core(mh_ctx *c, uint64_t n, const mh_tx_header *sh, const mh_tx_header *th,
-                       const uint8_t *md_blob, uint64_t md_blob_len, const uint64_t *incl_off,
-                       const uint8_t *incl_terms, const uint64_t *cons_off,
-                       const uint8_t *cons_terms, const uint64_t *src, const uint64_t *tgt,
-                       const uint8_t *src_alh, const uint8_t *tgt_alh, int32_t *status,
-                       bool alh_checked) {
-    MH_HIP(hipSetDevice(c->device));
-    const uint64_t ni = incl_off[n] - incl_off[0], nc = cons_off[n] - cons_off[0];
-    const uint64_t nh = alh_checked ? 0 : 2 * n;  // headers hashed here
-    // host-built inputs first (one contiguous upload), then device-only data
-    Layout L;
-    const uint64_t b_h = L.add(nh * sizeof(mh_tx_header)), b_x = L.add(2 * n * 32),
-                   b_sbl = L.add(n * 32), b_tbl = L.add(n * 32), b_sel = L.add(n),
-                   b_ii = L.add(n * 8), b_ij = L.add(n * 8), b_ci = L.add(n * 8),
-                   b_io = L.add((n + 1) * 8), b_co = L.add((n + 1) * 8);
-    const uint64_t up_bytes = L.total;
-    const uint64_t b_st = L.add(2 * n * 4), b_oki = L.add(n), b_okc = L.add(n);  // results
-    const uint64_t res0 = b_st, res_bytes = L.total - b_st;
-    const uint64_t b_md = L.add(alh_checked ? 0 : md_blob_len), b_s = L.add(nh * kTxInnerStride),
-                   b_leaf = L.add(n * 32), b_ca = L.add(n * 32), b_it = L.add(ni * 32),
-                   b_ct = L.add(nc * 32);
-    MH_HIP(c->p_stage.ensure(L.total));
-    uint8_t *hp = c->p_stage.as<uint8_t>();
-    mh_tx_header *hh = reinterpret_cast<mh_tx_header *>(hp + b_h);
-    uint8_t *x = hp + b_x, *sbl = hp + b_sbl, *tbl = hp + b_tbl, *sel = hp + b_sel;
-    uint64_t *ii = reinterpret_cast<uint64_t *>(hp + b_ii), *ij = reinterpret_cast<uint64_t *>(hp + b_ij),
-             *ci = reinterpret_cast<uint64_t *>(hp + b_ci), *io = reinterpret_cast<uint64_t *>(hp + b_io),
-             *co = reinterpret_cast<uint64_t *>(hp + b_co);
-    for (uint64_t p = 0; p < n; p++) {
-        if (!alh_checked) {
-            hh[p] = sh[p];
-            hh[n + p] = th[p];
-            if (status[p] != MH_OK) {  // keep the kernel's reads inside md_blob; result unused
-                hh[p].version = hh[n + p].version = 1;
-                hh[p].md_len = hh[n + p].md_len = 0;
-            }
-        }
-        memcpy(x + p * 32, src_alh + p * 32, 32);
-        memcpy(x + (n + p) * 32, tgt_alh + p * 32, 32);
-        ii[p] = src[p];  // verification.go:342-348
-        ij[p] = th[p].bl_tx_id;
-        sel[p] = src[p] == 1;  // :354-370
-        ci[p] = src[p] == 1 ? src[p] : sh[p].bl_tx_id;
-        memcpy(sbl + p * 32, sh[p].bl_root, 32);
-        memcpy(tbl + p * 32, th[p].bl_root, 32);
+// ---- VerifyDualProofV2: the one verifier behind the array and wire calls
+namespace {
+
+// dual_proof_v2_core's scratch: the operands k_dpv2_prep writes, the Alh
+// kernel's message area and every check's result
+struct Dpv2Scratch {
+    uint64_t hh, s, x, ast, sbl, tbl, leaf, ca, ii, ij, ci, sel, oki, okc, total;
+    explicit Dpv2Scratch(uint64_t n) {
+        Layout L;
+        hh = L.add(2 * n * sizeof(mh_tx_header)), s = L.add(2 * n * kTxInnerStride);
+        x = L.add(2 * n * 32), ast = L.add(2 * n * 4);
+        sbl = L.add(n * 32), tbl = L.add(n * 32), leaf = L.add(n * 32), ca = L.add(n * 32);
+        ii = L.add(n * 8), ij = L.add(n * 8), ci = L.add(n * 8);
+        sel = L.add(n), oki = L.add(n), okc = L.add(n);
+        total = L.total;
     }
-    for (uint64_t p = 0; p <= n; p++) {
-        io[p] = incl_off[p] - incl_off[0];
-        co[p] = cons_off[p] - cons_off[0];
-    }
-    MH_HIP(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    MH_HIP(c->s_tx.ensure(L.total));
-    uint8_t *base = c->s_tx.as<uint8_t>();
-    MH_HIP(hipMemcpyAsync(base, hp, up_bytes, hipMemcpyHostToDevice, st));
-    if (ni) MH_HIP(hipMemcpyAsync(base + b_it, incl_terms + incl_off[0] * 32, ni * 32,
-                                  hipMemcpyHostToDevice, st));
-    if (nc) MH_HIP(hipMemcpyAsync(base + b_ct, cons_terms + cons_off[0] * 32, nc * 32,
-                                  hipMemcpyHostToDevice, st));
-    if (!alh_checked) {
-        if (md_blob && md_blob_len)
-            MH_HIP(hipMemcpyAsync(base + b_md, md_blob, md_blob_len, hipMemcpyHostToDevice, st));
-        // Alh of both headers vs the given ones (verification.go:318-326)
-        MH_HIP(launch_tx_alh(st, c->tm(), 2 * n, (const MhTxHeader *)(base + b_h), base + b_md,
-                             nullptr, base + b_s, base + b_x, nullptr, nullptr, nullptr,
-                             (int32_t *)(base + b_st)));
-    } else {
-        MH_HIP(hipMemsetAsync(base + b_st, 0, 2 * n * 4, st));  // every Alh matched (MH_OK)
-    }
-    // leafFor(sourceAlh) (verification.go:346), then the two ahtree proofs
-    MH_HIP(launch_leaf_for(st, c->tm(), n, base + b_x, base + b_leaf));
-    MH_HIP(launch_ahtree_verify(st, c->tm(), MH_AHT_INCLUSION, n, (const uint64_t *)(base + b_ii),
-                                (const uint64_t *)(base + b_ij), (const uint64_t *)(base + b_io),
-                                base + b_it, base + b_leaf, base + b_tbl, base + b_oki, nullptr));
-    MH_HIP(launch_select32(st, n, base + b_sel, base + b_leaf, base + b_sbl, base + b_ca));
-    MH_HIP(launch_ahtree_verify(st, c->tm(), MH_AHT_CONSISTENCY, n,
-                                (const uint64_t *)(base + b_ci), (const uint64_t *)(base + b_ij),
-                                (const uint64_t *)(base + b_co), base + b_ct, base + b_ca,
-                                base + b_tbl, base + b_okc, nullptr));
-    MH_HIP(hipMemcpyAsync(hp + res0, base + res0, res_bytes, hipMemcpyDeviceToHost, st));
-    MH_HIP(hipStreamSynchronize(st));
-    const int32_t *ast = reinterpret_cast<const int32_t *>(hp + b_st);
-    const uint8_t *oki = hp + b_oki, *okc = hp + b_okc;
-    for (uint64_t p = 0; p < n; p++) {
-        if (status[p] != MH_OK) continue;
-        if (ast[p] != MH_OK || ast[n + p] != MH_OK) {
-            status[p] = MH_ERR_ILLEGAL_ARGUMENTS;
-        } else if (sh[p].id - 1 != sh[p].bl_tx_id || th[p].id - 1 != th[p].bl_tx_id) {
-            status[p] = MH_ERR_UNEXPECTED_LINKING;  // :328-330
-        } else if (src[p] == tgt[p]) {
-            status[p] = MH_OK;  // :332-334
-        } else if (!oki[p]) {
-            status[p] = MH_ERR_INCLUSION_NOT_VALID;
-        } else if (!okc[p]) {
-            status[p] = MH_ERR_CONSISTENCY_NOT_VALID;
-        }
-    }
+};
+
+}  // namespace
+
+uint64_t dual_proof_v2_scratch_bytes(uint64_t n) { return Dpv2Scratch(n).total; }
+
+int dual_proof_v2_core(hipStream_t st, Timer *tm, uint64_t n, const mh_tx_header *src_hdr,
+                       const mh_tx_header *tgt_hdr, const uint8_t *md_blob,
+                       const uint64_t *incl_off, const uint8_t *incl_terms,
+                       const uint64_t *cons_off, const uint8_t *cons_terms, const uint64_t *src,
+                       const uint64_t *tgt, const uint8_t *src_alh, const uint8_t *tgt_alh,
+                       const int32_t *status_in, uint64_t md_blob_len, Dp1V0Metadata v0_md,
+                       uint8_t *scratch, int32_t *status_out) {
+    const Dpv2Scratch S(n);
+    auto U = [&](uint64_t off) { return (uint64_t *)(scratch + off); };
+    mh_tx_header *hh = (mh_tx_header *)(scratch + S.hh);
+    int32_t *ast = (int32_t *)(scratch + S.ast);
+    uint8_t *x = scratch + S.x, *sel = scratch + S.sel, *sbl = scratch + S.sbl,
+            *tbl = scratch + S.tbl, *oki = scratch + S.oki, *okc = scratch + S.okc;
+    // argument checks (:305-316, and the header rules) and every operand
+    MH_HIP(launch_dpv2_prep(st, tm, n, src_hdr, tgt_hdr, md_blob != nullptr, src, tgt, src_alh,
+                            tgt_alh, status_in, md_blob_len, v0_md, hh, x, U(S.ii), U(S.ij),
+                            U(S.ci), sel, sbl, tbl, status_out));
+    // Alh of both headers vs the given ones (:318-326)
+    MH_HIP(launch_tx_alh(st, tm, 2 * n, hh, md_blob, nullptr, scratch + S.s, x, nullptr, nullptr,
+                         nullptr, ast));
+    // inclusion and consistency (:342-370), then the verdict
+    MH_HIP(launch_dpv2_proofs(st, tm, n, U(S.ii), U(S.ij), U(S.ci), sel, sbl, tbl, x, incl_off,
+                              incl_terms, cons_off, cons_terms, scratch + S.leaf, scratch + S.ca,
+                              oki, okc));
+    MH_HIP(launch_dpv2_verdict(st, tm, n, hh, src, tgt, ast, oki, okc, status_out));
     return MH_OK;
 }
 
+// The caller's per-proof arrays are packed whole into one pinned staging area
+// laid out like their device copies and go up in ONE copy; the offsets keep
+// their base and the term pointers are biased.  The statuses come back there.
 extern "C" int mh_verify_dual_proof_v2_batch(mh_ctx *c, uint64_t n, const mh_tx_header *sh,
                                              const mh_tx_header *th, const uint8_t *md_blob,
                                              uint64_t md_blob_len, const uint64_t *incl_off,
@@ -352,22 +297,50 @@ extern "C" int mh_verify_dual_proof_v2_batch(mh_ctx *c, uint64_t n, const mh_tx_
         if (!monotonic(incl_off, n) || !monotonic(cons_off, n)) return MH_ERR_ILLEGAL_ARGUMENTS;
         const uint64_t ni = incl_off[n] - incl_off[0], nc = cons_off[n] - cons_off[0];
         if ((ni && !incl_terms) || (nc && !cons_terms)) return MH_ERR_ILLEGAL_ARGUMENTS;
-        // verification.go:305-316: argument checks on the host, headers that
-        // cannot be hashed (unknown version, bad md) fail as ErrIllegalArguments
-        for (uint64_t p = 0; p < n; p++) {
-            int32_t s = MH_OK;
-            if (sh[p].id == 0 || sh[p].id != src[p] || th[p].id != tgt[p])
-                s = MH_ERR_ILLEGAL_ARGUMENTS;
-            else if (src[p] > tgt[p])
-                s = MH_ERR_SOURCE_TX_NEWER;
-            else if (check_header(sh[p], md_blob_len, md_blob != nullptr) ||
-                     check_header(th[p], md_blob_len, md_blob != nullptr))
-                s = MH_ERR_ILLEGAL_ARGUMENTS;
-            status[p] = s;
-        }
+        const uint64_t md_bytes = md_blob ? md_blob_len : 0, hb = n * sizeof(mh_tx_header);
         std::lock_guard<std::mutex> lk(c->mu);
-        return dual_proof_v2_core(c, n, sh, th, md_blob, md_blob_len, incl_off, incl_terms,
-                                  cons_off, cons_terms, src, tgt, src_alh, tgt_alh, status, false);
+        MH_HIP(hipSetDevice(c->device));
+        hipStream_t st = c->stream;
+        // the packed arrays first (one contiguous upload), then device-only data
+        Layout L;
+        const uint64_t b_h = L.add(2 * hb), b_src = L.add(n * 8), b_tgt = L.add(n * 8),
+                       b_alh = L.add(2 * n * 32), b_io = L.add((n + 1) * 8),
+                       b_co = L.add((n + 1) * 8);
+        const uint64_t up_bytes = L.total;
+        const uint64_t b_st = L.add(n * 4), b_md = L.add(md_bytes), b_it = L.add(ni * 32),
+                       b_ct = L.add(nc * 32), b_core = L.add(dual_proof_v2_scratch_bytes(n));
+        MH_HIP(c->p_stage.ensure(b_st + n * 4));
+        MH_HIP(c->s_tx.ensure(L.total));
+        uint8_t *hp = c->p_stage.as<uint8_t>(), *base = c->s_tx.as<uint8_t>();
+        memcpy(hp + b_h, sh, hb);
+        memcpy(hp + b_h + hb, th, hb);
+        memcpy(hp + b_src, src, n * 8);
+        memcpy(hp + b_tgt, tgt, n * 8);
+        memcpy(hp + b_alh, src_alh, n * 32);
+        memcpy(hp + b_alh + n * 32, tgt_alh, n * 32);
+        memcpy(hp + b_io, incl_off, (n + 1) * 8);
+        memcpy(hp + b_co, cons_off, (n + 1) * 8);
+        MH_HIP(hipMemcpyAsync(base, hp, up_bytes, hipMemcpyHostToDevice, st));
+        if (ni) MH_HIP(hipMemcpyAsync(base + b_it, incl_terms + incl_off[0] * 32, ni * 32,
+                                      hipMemcpyHostToDevice, st));
+        if (nc) MH_HIP(hipMemcpyAsync(base + b_ct, cons_terms + cons_off[0] * 32, nc * 32,
+                                      hipMemcpyHostToDevice, st));
+        if (md_bytes)
+            MH_HIP(hipMemcpyAsync(base + b_md, md_blob, md_bytes, hipMemcpyHostToDevice, st));
+        // check_header's rule: a v0 header with metadata fails the proof
+        const mh_tx_header *dh = (const mh_tx_header *)(base + b_h);
+        if (int e = dual_proof_v2_core(
+                st, c->tm(), n, dh, dh + n, md_blob ? base + b_md : nullptr,
+                (const uint64_t *)(base + b_io), base + b_it - incl_off[0] * 32,
+                (const uint64_t *)(base + b_co), base + b_ct - cons_off[0] * 32,
+                (const uint64_t *)(base + b_src), (const uint64_t *)(base + b_tgt), base + b_alh,
+                base + b_alh + n * 32, nullptr, md_bytes, kDp1V0MetadataRefused, base + b_core,
+                (int32_t *)(base + b_st)))
+            return e;
+        MH_HIP(hipMemcpyAsync(hp + b_st, base + b_st, n * 4, hipMemcpyDeviceToHost, st));
+        MH_HIP(hipStreamSynchronize(st));
+        memcpy(status, hp + b_st, n * 4);
+        return MH_OK;
     });
 }
 

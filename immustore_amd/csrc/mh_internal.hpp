@@ -263,11 +263,11 @@ struct Dual1Arrays {
     uint64_t *lin_src, *lin_tgt;
 };
 
-// The one intended difference between the callers of the v1 verifier: what a
-// v0 header that carries metadata means.  Go's innerHash never reads a v0
-// header's metadata (tx.go:258-263), so for headers decoded from the wire it
-// is dropped and the proof goes on; the array call keeps check_header's rule
-// (MH_ERR_METADATA_UNSUPPORTED) and the proof is false.
+// The one intended difference between the callers of a dual-proof verifier
+// (v1 and V2 alike): what a v0 header that carries metadata means.  Go's
+// innerHash never reads a v0 header's metadata (tx.go:258-263), so for headers
+// decoded from the wire it is dropped and the proof goes on; the array calls
+// keep check_header's rule (MH_ERR_METADATA_UNSUPPORTED) and the proof fails.
 enum Dp1V0Metadata : int { kDp1V0MetadataDropped = 0, kDp1V0MetadataRefused = 1 };
 
 struct Dp1Ops {        // per-proof operands of one batch (n entries unless noted)
@@ -293,6 +293,59 @@ struct Dp1Results {  // per-check results: n each, qok per nested proof from fir
 hipError_t launch_dp1_verdict(hipStream_t st, Timer *tm, uint64_t n, const Dp1Ops &w,
                               const Dp1Results &r, const uint8_t *has_lin, const uint64_t *first,
                               uint8_t *ok);
+
+__device__ __forceinline__ void copy32_a8(uint8_t *d, const uint8_t *s) {  // both 8-byte aligned
+    const uint2 *a = (const uint2 *)s;
+    uint2 *b = (uint2 *)d;
+#pragma unroll
+    for (int i = 0; i < 4; i++) b[i] = a[i];
+}
+
+// ---- VerifyDualProofV2 (verification.go:303-372) over device arrays
+// Its rules, each written once, for k_dpv2_prep / k_dpv2_verdict and the
+// document verifier's kernels (capi_doc.hip).  The operands of proof p's two
+// ahtree proofs (:342-370); headers in device memory, sbl / tbl n x 32
+__device__ __forceinline__ void dpv2_operands(uint64_t p, uint64_t src, const mh_tx_header *sh,
+                                              const mh_tx_header *th, uint64_t *ii, uint64_t *ij,
+                                              uint64_t *ci, uint8_t *sel, uint8_t *sbl,
+                                              uint8_t *tbl) {
+    ii[p] = src;
+    ij[p] = th->bl_tx_id;
+    sel[p] = src == 1;  // consistency of leafFor(sourceAlh) itself, :354-357
+    ci[p] = src == 1 ? src : sh->bl_tx_id;
+    copy32_a8(sbl + 32 * p, sh->bl_root);
+    copy32_a8(tbl + 32 * p, th->bl_root);
+}
+// The status of a proof that passed the argument and Alh checks (:328-370)
+__device__ __forceinline__ int32_t dpv2_ladder(const mh_tx_header *sh, const mh_tx_header *th,
+                                               bool same_id, bool oki, bool okc) {
+    if (sh->id - 1 != sh->bl_tx_id || th->id - 1 != th->bl_tx_id)
+        return MH_ERR_UNEXPECTED_LINKING;  // :328-330
+    if (same_id) return MH_OK;             // :332-334
+    return !oki ? MH_ERR_INCLUSION_NOT_VALID : !okc ? MH_ERR_CONSISTENCY_NOT_VALID : MH_OK;
+}
+
+// argument checks + operands (k_dpv2_prep): hh 2 n headers for the Alh kernel
+// and x 2 n x 32 Alh values, sources then targets; have_blob as for
+// dp1_header_ok; status_in may be null or status_out
+hipError_t launch_dpv2_prep(hipStream_t st, Timer *tm, uint64_t n, const mh_tx_header *src_hdr,
+                            const mh_tx_header *tgt_hdr, bool have_blob, const uint64_t *src,
+                            const uint64_t *tgt, const uint8_t *src_alh, const uint8_t *tgt_alh,
+                            const int32_t *status_in, uint64_t md_blob_len, Dp1V0Metadata v0_md,
+                            mh_tx_header *hh, uint8_t *x, uint64_t *ii, uint64_t *ij,
+                            uint64_t *ci, uint8_t *sel, uint8_t *sbl, uint8_t *tbl,
+                            int32_t *status_out);
+// leafFor(sourceAlh) (:346), inclusion, select, consistency; leaf / ca n x 32
+hipError_t launch_dpv2_proofs(hipStream_t st, Timer *tm, uint64_t n, const uint64_t *ii,
+                              const uint64_t *ij, const uint64_t *ci, const uint8_t *sel,
+                              const uint8_t *sbl, const uint8_t *tbl, const uint8_t *src_alh_x,
+                              const uint64_t *incl_off, const uint8_t *incl_terms,
+                              const uint64_t *cons_off, const uint8_t *cons_terms, uint8_t *leaf,
+                              uint8_t *ca, uint8_t *oki, uint8_t *okc);
+// the verdict of every proof still MH_OK (:318-370); ast: the 2 n Alh statuses
+hipError_t launch_dpv2_verdict(hipStream_t st, Timer *tm, uint64_t n, const mh_tx_header *hh,
+                               const uint64_t *src, const uint64_t *tgt, const int32_t *ast,
+                               const uint8_t *oki, const uint8_t *okc, int32_t *status);
 // roots of many htrees (widths leaf_off[t+1]-leaf_off[t], small), one lane
 // each, in place over nodes = their leaf hashes back to back
 constexpr uint64_t kSmallTreeMax = 64;

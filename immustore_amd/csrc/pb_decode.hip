@@ -497,73 +497,6 @@ __global__ __launch_bounds__(256) void k_pbd_dual1(uint64_t n, const uint8_t *__
     if (lt) md_write(mt, o.md_blob + m0 + ls);
 }
 
-// ------------------------------------------- DualProofV2 from the wire, verified
-// VerifyDualProofV2's argument checks (verification.go:303-316) and the arrays
-// of its two ahtree proofs (:342-370) from the decoded headers, on the device
-// (the host loops of mh_verify_dual_proof_v2_batch); headers that cannot be
-// hashed are flagged and hashed as empty v1 headers.  Decoded metadata is
-// canonical and at most 268 bytes, so only the version can make a header
-// unhashable here.
-__global__ __launch_bounds__(256) void k_dpv2_prep(uint64_t n, const mh_tx_header *__restrict__ hd,
-                                                   const uint64_t *__restrict__ src,
-                                                   const uint64_t *__restrict__ tgt,
-                                                   int32_t *__restrict__ status,
-                                                   mh_tx_header *__restrict__ hh,
-                                                   uint64_t *__restrict__ ii, uint64_t *__restrict__ ij,
-                                                   uint64_t *__restrict__ ci, uint8_t *__restrict__ sel,
-                                                   uint8_t *__restrict__ sbl, uint8_t *__restrict__ tbl) {
-    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    mh_tx_header sh = hd[p], th = hd[n + p];
-    int32_t s = status[p];
-    // a v0 innerHash never reads the metadata (tx.go:258-263), which a wire
-    // header may carry; a version other than 0 / 1 panics in Go's innerHash
-    if (sh.version == 0) sh.md_len = 0;
-    if (th.version == 0) th.md_len = 0;
-    if (s == MH_OK) {
-        if (sh.id == 0 || sh.id != src[p] || th.id != tgt[p]) s = MH_ERR_ILLEGAL_ARGUMENTS;
-        else if (src[p] > tgt[p]) s = MH_ERR_SOURCE_TX_NEWER;
-        else if (sh.version > 1 || th.version > 1) s = MH_ERR_ILLEGAL_ARGUMENTS;
-    }
-    status[p] = s;
-    ii[p] = src[p];
-    ij[p] = th.bl_tx_id;
-    sel[p] = src[p] == 1;
-    ci[p] = src[p] == 1 ? src[p] : sh.bl_tx_id;
-    for (int k = 0; k < 32; k++) {
-        sbl[32 * p + k] = sh.bl_root[k];
-        tbl[32 * p + k] = th.bl_root[k];
-    }
-    if (s != MH_OK) {  // keep the Alh kernel's reads inside md_blob; result unused
-        sh.version = th.version = 1;
-        sh.md_len = th.md_len = 0;
-    }
-    hh[p] = sh;
-    hh[n + p] = th;
-}
-
-// verification.go:318-370 after the Alh values and the two ahtree proofs
-__global__ __launch_bounds__(256) void k_dpv2_final(uint64_t n, const mh_tx_header *__restrict__ hd,
-                                                    const uint64_t *__restrict__ src,
-                                                    const uint64_t *__restrict__ tgt,
-                                                    const int32_t *__restrict__ alh_st,
-                                                    const uint8_t *__restrict__ oki,
-                                                    const uint8_t *__restrict__ okc,
-                                                    int32_t *__restrict__ status) {
-    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    int32_t s = status[p];
-    if (s == MH_OK) {
-        const mh_tx_header &sh = hd[p], &th = hd[n + p];
-        if (alh_st[p] != MH_OK || alh_st[n + p] != MH_OK) s = MH_ERR_ILLEGAL_ARGUMENTS;
-        else if (sh.id - 1 != sh.bl_tx_id || th.id - 1 != th.bl_tx_id) s = MH_ERR_UNEXPECTED_LINKING;
-        else if (src[p] == tgt[p]) s = MH_OK;
-        else if (!oki[p]) s = MH_ERR_INCLUSION_NOT_VALID;
-        else if (!okc[p]) s = MH_ERR_CONSISTENCY_NOT_VALID;
-    }
-    status[p] = s;
-}
-
 // Two device words into pinned host memory by a kernel store: a small
 // read-back without a DMA copy, which would queue behind the large
 // host-to-device chunks in flight on the copy engine.
@@ -861,8 +794,10 @@ extern "C" int mh_dual_proof_pb_decode_batch(mh_ctx *c, uint64_t n, const uint8_
 }
 
 // DualProofV2 straight from the wire, in the chunk frame of PbChunkFrame
-// (capi_internal.hpp): chunk k is decoded and verified on the compute stream
-// as soon as its copy has landed.
+// (capi_internal.hpp): chunk k is decoded and verified by dual_proof_v2_core
+// (capi_tx.hip; with kDp1V0MetadataDropped) on the compute stream as soon as
+// its copy has landed.  The verifier's scratch is sized for the largest chunk
+// and reused chunk after chunk (one compute stream orders them).
 extern "C" int mh_verify_dual_proof_v2_pb_batch(mh_ctx *c, uint64_t n, const uint8_t *msgs,
                                                 const uint64_t *msg_off, const uint64_t *src,
                                                 const uint64_t *tgt, const uint8_t *src_alh,
@@ -883,19 +818,17 @@ extern "C" int mh_verify_dual_proof_v2_pb_batch(mh_ctx *c, uint64_t n, const uin
         MH_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const uint64_t *)nullptr,
                                                 (uint64_t *)nullptr, (int)max_nk, st));
         Layout L;
-        // caller arrays (x = per chunk: its source Alh values then its target
-        // Alh values, as the Alh kernel expects them), then device-only data;
-        // per-chunk offset arrays hold n_k + 1 entries at [lo + k, hi + k]
+        // caller arrays (xa: the source Alh values, then the target ones), the
+        // decode's arrays (per-chunk offset arrays hold n_k + 1 entries at
+        // [lo + k, hi + k]), then one chunk's verifier scratch
         const uint64_t nc = n + (uint64_t)nch;
         const uint64_t b_msg = L.add(mb + 16), b_off = L.add((n + 1) * 8), b_src = L.add(n * 8),
-                       b_tgt = L.add(n * 8), b_xa = L.add(2 * n * 32), b_x = L.add(2 * n * 32),
-                       b_cnt = L.add(3 * n * 8), b_io = L.add(nc * 8), b_co = L.add(nc * 8), b_mo = L.add(nc * 8),
+                       b_tgt = L.add(n * 8), b_xa = L.add(2 * n * 32), b_cnt = L.add(3 * n * 8),
+                       b_io = L.add(nc * 8), b_co = L.add(nc * 8), b_mo = L.add(nc * 8),
                        b_st = L.add(n * 4), b_scan = L.add(scan_bytes),
-                       b_hd = L.add(2 * n * sizeof(mh_tx_header)), b_hh = L.add(2 * n * sizeof(mh_tx_header)),
-                       b_md = L.add(2 * n * (uint64_t)kMdSlot), b_s = L.add(2 * n * kTxInnerStride),
-                       b_ast = L.add(2 * n * 4), b_ii = L.add(n * 8), b_ij = L.add(n * 8),
-                       b_ci = L.add(n * 8), b_sel = L.add(n), b_sbl = L.add(n * 32), b_tbl = L.add(n * 32),
-                       b_leaf = L.add(n * 32), b_ca = L.add(n * 32), b_oki = L.add(n), b_okc = L.add(n);
+                       b_hd = L.add(2 * n * sizeof(mh_tx_header)),
+                       b_md = L.add(2 * n * (uint64_t)kMdSlot),
+                       b_core = L.add(dual_proof_v2_scratch_bytes(max_nk));
         MH_HIP(c->s_tx.ensure(L.total));
         // term area reused chunk after chunk: a well-formed term costs >= 34
         // message bytes (tag, length, 32-byte digest), so this rarely grows;
@@ -943,40 +876,18 @@ extern "C" int mh_verify_dual_proof_v2_pb_batch(mh_ctx *c, uint64_t n, const uin
             MH_HIP(hipStreamSynchronize(st));
             MH_HIP(tb.ensure(std::max<uint64_t>(tot[0] + tot[1], 1) * 32));
             uint8_t *dti = tb.as<uint8_t>(), *dtc = dti + tot[0] * 32;
-            mh_tx_header *hd = (mh_tx_header *)(base + b_hd) + 2 * lo,
-                         *hh = (mh_tx_header *)(base + b_hh) + 2 * lo;
+            mh_tx_header *hd = (mh_tx_header *)(base + b_hd) + 2 * lo;
             hipLaunchKernelGGL(k_pbd_dual<true>, dim3(grid), dim3(256), 0, st, nk, dmsg, doff,
                                nullptr, nullptr, nullptr, io, co, mo, dti, dtc, hd, hd + nk, md, dst);
             MH_HIP(hipGetLastError());
             // VerifyDualProofV2 (verification.go:303-370)
-            uint64_t *ii = (uint64_t *)(base + b_ii) + lo, *ij = (uint64_t *)(base + b_ij) + lo,
-                     *ci = (uint64_t *)(base + b_ci) + lo;
-            const uint64_t *dsrc = (const uint64_t *)(base + b_src) + lo,
-                           *dtgt = (const uint64_t *)(base + b_tgt) + lo;
-            uint8_t *x = base + b_x + 2 * lo * 32, *leaf = base + b_leaf + lo * 32,
-                    *sbl = base + b_sbl + lo * 32, *tbl = base + b_tbl + lo * 32,
-                    *ca = base + b_ca + lo * 32, *sel = base + b_sel + lo, *oki = base + b_oki + lo,
-                    *okc = base + b_okc + lo;
-            int32_t *ast = (int32_t *)(base + b_ast) + 2 * lo;
-            // the chunk's Alh values source-then-target, as the Alh kernel reads them
-            MH_HIP(hipMemcpyAsync(x, base + b_xa + lo * 32, nk * 32, hipMemcpyDeviceToDevice, st));
-            MH_HIP(hipMemcpyAsync(x + nk * 32, base + b_xa + (n + lo) * 32, nk * 32,
-                                  hipMemcpyDeviceToDevice, st));
-            hipLaunchKernelGGL(k_dpv2_prep, dim3(grid), dim3(256), 0, st, nk, hd, dsrc, dtgt, dst, hh,
-                               ii, ij, ci, sel, sbl, tbl);
-            MH_HIP(hipGetLastError());
-            MH_HIP(launch_tx_alh(st, c->tm(), 2 * nk, hh, md, nullptr,
-                                 base + b_s + 2 * lo * kTxInnerStride, x, nullptr, nullptr, nullptr,
-                                 ast));
-            MH_HIP(launch_leaf_for(st, c->tm(), nk, x, leaf));
-            MH_HIP(launch_ahtree_verify(st, c->tm(), MH_AHT_INCLUSION, nk, ii, ij, io, dti, leaf,
-                                        tbl, oki, nullptr));
-            MH_HIP(launch_select32(st, nk, sel, leaf, sbl, ca));
-            MH_HIP(launch_ahtree_verify(st, c->tm(), MH_AHT_CONSISTENCY, nk, ci, ij, co, dtc, ca,
-                                        tbl, okc, nullptr));
-            hipLaunchKernelGGL(k_dpv2_final, dim3(grid), dim3(256), 0, st, nk, hd, dsrc, dtgt, ast,
-                               oki, okc, dst);
-            MH_HIP(hipGetLastError());
+            if (int e = dual_proof_v2_core(st, c->tm(), nk, hd, hd + nk, md, io, dti, co, dtc,
+                                           (const uint64_t *)(base + b_src) + lo,
+                                           (const uint64_t *)(base + b_tgt) + lo,
+                                           base + b_xa + lo * 32, base + b_xa + (n + lo) * 32, dst,
+                                           2 * nk * (uint64_t)kMdSlot, kDp1V0MetadataDropped,
+                                           base + b_core, dst))
+                return e;
         }
         MH_HIP(cc.join());
         MH_HIP(hipMemcpyAsync(status, dst_all, n * 4, hipMemcpyDeviceToHost, st));

@@ -220,13 +220,6 @@ __global__ __launch_bounds__(256) void k_advance_chain_gated(
 // hash: the argument checks and operands before the checks, the verdict after
 // them.  dual_proof_v1_core (capi_tx.hip) strings them together.
 
-__device__ __forceinline__ void copy32(uint8_t *d, const uint8_t *s) {  // both 8-byte aligned
-    const uint2 *a = (const uint2 *)s;
-    uint2 *b = (uint2 *)d;
-#pragma unroll
-    for (int i = 0; i < 4; i++) b[i] = a[i];
-}
-
 // check_header's rule (capi_internal.hpp) on a header's fields; v0_md: what a
 // v0 header with metadata means to this caller (Dp1V0Metadata)
 __device__ __forceinline__ bool dp1_header_ok(uint32_t version, uint32_t md_len, uint32_t md_off,
@@ -273,12 +266,12 @@ __global__ __launch_bounds__(256) void k_dp1_prep(uint64_t n, Dual1Arrays o,
     w.ij[p] = tbl_id;
     w.ci[p] = sbl_id;
     w.ls[p] = a_branch ? tbl_id : s;
-    copy32(w.x + 32 * p, sa);
-    copy32(w.x + 32 * (n + p), tgt_alh + 32 * p);
-    copy32(w.sbl + 32 * p, sh->bl_root);
-    copy32(w.tbl + 32 * p, th->bl_root);
-    copy32(w.lin_sa + 32 * p, a_branch ? tba : sa);
-    copy32(w.end_alh + 32 * p, a_branch ? sa : tba);
+    copy32_a8(w.x + 32 * p, sa);
+    copy32_a8(w.x + 32 * (n + p), tgt_alh + 32 * p);
+    copy32_a8(w.sbl + 32 * p, sh->bl_root);
+    copy32_a8(w.tbl + 32 * p, th->bl_root);
+    copy32_a8(w.lin_sa + 32 * p, a_branch ? tba : sa);
+    copy32_a8(w.end_alh + 32 * p, a_branch ? sa : tba);
     const uint64_t start = sbl_id, end = a_branch ? s : tbl_id;
     uint8_t state;
     if (end < start) state = 2;
@@ -328,7 +321,7 @@ __global__ __launch_bounds__(256) void k_dp1_nested(uint64_t nq, uint64_t n,
     const bool run = a_state[lo] == 0;
     qi[q] = run ? a_start[lo] + 1 + (g - first[lo]) : 0;
     qj[q] = run ? ij[lo] : 0;
-    copy32(qroot + 32 * q, tbl + 32 * lo);
+    copy32_a8(qroot + 32 * q, tbl + 32 * lo);
 }
 
 // The verdict in Go's order (verification.go:140-235), one proof per lane,
@@ -359,6 +352,63 @@ __global__ __launch_bounds__(256) void k_dp1_verdict(
         }
     }
     ok[p] = r ? 1 : 0;
+}
+
+// ------------------------------------------- VerifyDualProofV2 around the checks
+// The same for store.VerifyDualProofV2 (verification.go:303-372), strung
+// together by dual_proof_v2_core: the argument checks in Go's order
+// (:305-316), then the headers that cannot be hashed, and the operands.  Dead
+// proofs and v0 metadata are hashed as in k_dp1_prep.
+__global__ __launch_bounds__(256) void k_dpv2_prep(
+    uint64_t n, const mh_tx_header *__restrict__ src_hdr, const mh_tx_header *__restrict__ tgt_hdr,
+    bool have_blob, const uint64_t *__restrict__ src, const uint64_t *__restrict__ tgt,
+    const uint8_t *__restrict__ src_alh, const uint8_t *__restrict__ tgt_alh,
+    const int32_t *status_in, uint64_t md_blob_len, int v0_md, mh_tx_header *__restrict__ hh,
+    uint8_t *__restrict__ x, uint64_t *ii, uint64_t *ij, uint64_t *ci, uint8_t *sel, uint8_t *sbl,
+    uint8_t *tbl, int32_t *status_out) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    // headers read field by field and copied memory to memory (see k_dp1_prep)
+    const mh_tx_header *sh = src_hdr + p, *th = tgt_hdr + p;
+    const uint64_t s = src[p], t = tgt[p], sid = sh->id;
+    const uint32_t sv = sh->version, tv = th->version;
+    int32_t r = status_in ? status_in[p] : MH_OK;
+    if (r == MH_OK) {
+        if (sid == 0 || sid != s || th->id != t) r = MH_ERR_ILLEGAL_ARGUMENTS;
+        else if (s > t) r = MH_ERR_SOURCE_TX_NEWER;
+        else if (!dp1_header_ok(sv, sh->md_len, sh->md_off, md_blob_len, have_blob, v0_md) ||
+                 !dp1_header_ok(tv, th->md_len, th->md_off, md_blob_len, have_blob, v0_md))
+            r = MH_ERR_ILLEGAL_ARGUMENTS;
+    }
+    status_out[p] = r;
+    dpv2_operands(p, s, sh, th, ii, ij, ci, sel, sbl, tbl);
+    copy32_a8(x + 32 * p, src_alh + 32 * p);
+    copy32_a8(x + 32 * (n + p), tgt_alh + 32 * p);
+    const uint2 *hs = (const uint2 *)sh, *ht = (const uint2 *)th;
+    uint2 *ds = (uint2 *)(hh + p), *dd = (uint2 *)(hh + n + p);
+#pragma unroll
+    for (uint32_t i = 0; i < sizeof(mh_tx_header) / 8; i++) {
+        ds[i] = hs[i];
+        dd[i] = ht[i];
+    }
+    if (r != MH_OK) hh[p].version = hh[n + p].version = 1;
+    if (r != MH_OK || sv == 0) hh[p].md_len = 0;
+    if (r != MH_OK || tv == 0) hh[n + p].md_len = 0;
+}
+
+// verification.go:318-370 after the Alh values and the two ahtree proofs
+__global__ __launch_bounds__(256) void k_dpv2_verdict(uint64_t n, const mh_tx_header *__restrict__ hh,
+                                                      const uint64_t *__restrict__ src,
+                                                      const uint64_t *__restrict__ tgt,
+                                                      const int32_t *__restrict__ ast,
+                                                      const uint8_t *__restrict__ oki,
+                                                      const uint8_t *__restrict__ okc,
+                                                      int32_t *__restrict__ status) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n || status[p] != MH_OK) return;
+    status[p] = (ast[p] != MH_OK || ast[n + p] != MH_OK)
+                    ? MH_ERR_ILLEGAL_ARGUMENTS  // :318-326
+                    : dpv2_ladder(hh + p, hh + n + p, src[p] == tgt[p], oki[p], okc[p]);
 }
 
 // Entry digest (tx.go:690-731) -- and, with leaf != 0, its htree leaf
@@ -967,6 +1017,46 @@ hipError_t launch_dp1_verdict(hipStream_t st, Timer *tm, uint64_t n, const Dp1Op
     hipLaunchKernelGGL(k_dp1_verdict, dim3(grid_for(n, 256)), dim3(256), 0, st, n, w.alive, r.ast,
                        w.ii, w.ij, w.ci, r.oki, r.okc, r.okl, has_lin, r.oklin, w.a_state, w.a_cnt,
                        first, r.aok, r.qok, ok);
+    return hipGetLastError();
+}
+
+hipError_t launch_dpv2_prep(hipStream_t st, Timer *tm, uint64_t n, const mh_tx_header *src_hdr,
+                            const mh_tx_header *tgt_hdr, bool have_blob, const uint64_t *src,
+                            const uint64_t *tgt, const uint8_t *src_alh, const uint8_t *tgt_alh,
+                            const int32_t *status_in, uint64_t md_blob_len, Dp1V0Metadata v0_md,
+                            mh_tx_header *hh, uint8_t *x, uint64_t *ii, uint64_t *ij,
+                            uint64_t *ci, uint8_t *sel, uint8_t *sbl, uint8_t *tbl,
+                            int32_t *status_out) {
+    if (!n) return hipSuccess;
+    TimerScope ts(tm, "dpv2_prep", st);
+    hipLaunchKernelGGL(k_dpv2_prep, dim3(grid_for(n, 256)), dim3(256), 0, st, n, src_hdr, tgt_hdr,
+                       have_blob, src, tgt, src_alh, tgt_alh, status_in, md_blob_len, (int)v0_md, hh,
+                       x, ii, ij, ci, sel, sbl, tbl, status_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_dpv2_proofs(hipStream_t st, Timer *tm, uint64_t n, const uint64_t *ii,
+                              const uint64_t *ij, const uint64_t *ci, const uint8_t *sel,
+                              const uint8_t *sbl, const uint8_t *tbl, const uint8_t *src_alh_x,
+                              const uint64_t *incl_off, const uint8_t *incl_terms,
+                              const uint64_t *cons_off, const uint8_t *cons_terms, uint8_t *leaf,
+                              uint8_t *ca, uint8_t *oki, uint8_t *okc) {
+    if (hipError_t e = launch_leaf_for(st, tm, n, src_alh_x, leaf)) return e;
+    if (hipError_t e = launch_ahtree_verify(st, tm, MH_AHT_INCLUSION, n, ii, ij, incl_off,
+                                            incl_terms, leaf, tbl, oki, nullptr))
+        return e;
+    if (hipError_t e = launch_select32(st, n, sel, leaf, sbl, ca)) return e;
+    return launch_ahtree_verify(st, tm, MH_AHT_CONSISTENCY, n, ci, ij, cons_off, cons_terms, ca,
+                                tbl, okc, nullptr);
+}
+
+hipError_t launch_dpv2_verdict(hipStream_t st, Timer *tm, uint64_t n, const mh_tx_header *hh,
+                               const uint64_t *src, const uint64_t *tgt, const int32_t *ast,
+                               const uint8_t *oki, const uint8_t *okc, int32_t *status) {
+    if (!n) return hipSuccess;
+    TimerScope ts(tm, "dpv2_verdict", st);
+    hipLaunchKernelGGL(k_dpv2_verdict, dim3(grid_for(n, 256)), dim3(256), 0, st, n, hh, src, tgt,
+                       ast, oki, okc, status);
     return hipGetLastError();
 }
 

@@ -213,21 +213,161 @@ DUAL_V2_STATUSES = {U.ST_OK, U.ST_ILLEGAL, U.ST_NEWER, U.ST_LINKING, U.ST_INCLUS
                     U.ST_CONSISTENCY}
 
 
-def test_dual_v2_status_order(m, ctx):
-    """(f): one fault per branch of dual_proof_v2_core and two at once, the
-    status of the earlier rule; every status appears."""
+def _dual_v2(m, ctx, c, k=0, blob=None, blob_len=None):
+    """mh_verify_dual_proof_v2_batch over c -> status int32[n - k].  k > 0:
+    rows [k, n) addressed as a slice of the batch -- incl_off + k, cons_off +
+    k, the term arrays whole.  blob: the bytes passed instead of c.blob (False:
+    a null pointer), blob_len: the length given for them."""
     N = m._native
+    if blob is None:
+        blob = np.frombuffer(c.blob, np.uint8)
+    st = np.full(c.n - k, -1, np.int32)
+    N.check(N.load().mh_verify_dual_proof_v2_batch(
+        ctx.handle, c.n - k, c.sh[k:].ctypes.data, c.th[k:].ctypes.data,
+        None if blob is False else blob.ctypes.data, blob.size if blob_len is None else blob_len,
+        c.incl_off[k:].ctypes.data, c.incl.ctypes.data, c.cons_off[k:].ctypes.data,
+        c.cons.ctypes.data, c.s[k:].ctypes.data, c.t[k:].ctypes.data, c.sa[k:].ctypes.data,
+        c.ta[k:].ctypes.data, st.ctypes.data))
+    return st
+
+
+def _dual_v2_take(c, idx):
+    """the rows idx of a DualCorpus as a corpus of their own (copies)"""
+    d = U.DualCorpus()
+    d.n, d.blob, d.label = len(idx), c.blob, [c.label[p] for p in idx]
+    for f in ("sh", "th", "s", "t", "sa", "ta"):
+        setattr(d, f, getattr(c, f)[idx].copy())
+    for name in ("incl", "cons"):
+        off, terms = getattr(c, name + "_off"), getattr(c, name)
+        parts = [terms[int(off[p]):int(off[p + 1])] for p in idx]
+        o = np.zeros(d.n + 1, np.uint64)
+        o[1:] = np.cumsum([len(x) for x in parts], dtype=np.uint64)
+        setattr(d, name + "_off", o)
+        setattr(d, name, np.ascontiguousarray(np.concatenate(parts + [np.zeros((1, 32), np.uint8)])))
+    return d
+
+
+@pytest.fixture(scope="module")
+def dual_v2_full(m, ctx):
+    """the whole corpus through the array call, once"""
+    return _dual_v2(m, ctx, U.dual_v2_rows())
+
+
+def test_dual_v2_status_order(m, ctx, dual_v2_full):
+    """(f): one fault per rule of VerifyDualProofV2 and two at once, the
+    status of the earlier rule; every status appears.  The rules run on the
+    device, behind dual_proof_v2_core: the argument and header checks in
+    k_dpv2_prep, the Alh check and dpv2_ladder in k_dpv2_verdict."""
     c = U.dual_v2_rows()
     want = U.oracle_dual_v2_status()
     assert set(want.tolist()) == DUAL_V2_STATUSES
-    blob = np.frombuffer(c.blob, np.uint8)
-    st = np.full(c.n, -1, np.int32)
-    N.check(N.load().mh_verify_dual_proof_v2_batch(
-        ctx.handle, c.n, c.sh.ctypes.data, c.th.ctypes.data, blob.ctypes.data, blob.size,
-        c.incl_off.ctypes.data, c.incl.ctypes.data, c.cons_off.ctypes.data, c.cons.ctypes.data,
-        c.s.ctypes.data, c.t.ctypes.data, c.sa.ctypes.data, c.ta.ctypes.data, st.ctypes.data))
+    st = dual_v2_full
     _same(c, st, want, "DualProofV2 status")
     assert set(st.tolist()) == DUAL_V2_STATUSES
+
+
+def test_dual_v2_header_rules(m, ctx):
+    """The header rule of the array call -- check_header, each nonzero result
+    MH_ERR_ILLEGAL_ARGUMENTS -- on linked pairs that verify, every other row
+    left as it is (status 0): a version above 1 in either header, a v0 header
+    with metadata, metadata longer than MH_MAX_TX_METADATA_LEN, metadata
+    ending one byte past the blob and, in a call of its own, metadata without
+    a blob.  The rule comes after src > tgt and after the id rules.  The blob
+    passed has 1 KiB behind the length given for it, so that no row could read
+    outside it even without the rule.  Not compared with the oracle, which
+    takes no blob length."""
+    c = U.dual_v2_rows()
+    MAX_MD = 268  # MH_MAX_TX_METADATA_LEN
+    good = np.array([x.startswith("linked") for x in c.label]) & (c.s < c.t) & \
+        (c.sh["md_len"] == 0) & (c.th["md_len"] == 0) & (U.oracle_dual_v2_status() == 0)
+    idx = np.nonzero(good)[0][:16]
+    assert len(idx) == 16
+    L = len(c.blob)
+    blob = np.frombuffer(c.blob + bytes(1024), np.uint8)
+    d = _dual_v2_take(c, idx)
+    assert not _dual_v2(m, ctx, d, blob=blob, blob_len=L).any()
+    faults = {1: ("sh", dict(version=2)), 3: ("th", dict(version=2)),
+              5: ("sh", dict(version=0, md_len=5)), 7: ("th", dict(version=1, md_len=MAX_MD + 1)),
+              9: ("sh", dict(version=1, md_off=L - 3, md_len=4)),
+              # two at once: with src > tgt, with a wrong header id
+              11: ("th", dict(version=2)), 13: ("sh", dict(version=1, md_len=MAX_MD + 1))}
+    want = np.zeros(d.n, np.int32)
+    for p, (which, kw) in faults.items():
+        for f, v in kw.items():
+            getattr(d, which)[f][p] = v
+        want[p] = U.ST_ILLEGAL
+    for a, b in ((d.sh, d.th), (d.s, d.t), (d.sa, d.ta)):  # row 11: src > tgt, ids in step
+        a[11], b[11] = b[11].copy(), a[11].copy()
+    want[11] = U.ST_NEWER
+    d.th["id"][13] += 1
+    _same(d, _dual_v2(m, ctx, d, blob=blob, blob_len=L), want, "DualProofV2 header rules")
+    # metadata without a blob
+    d = _dual_v2_take(c, idx)
+    for h, p in ((d.sh, 2), (d.th, 6)):
+        h["version"][p], h["md_len"][p] = 1, 4
+    want = np.zeros(d.n, np.int32)
+    want[[2, 6]] = U.ST_ILLEGAL
+    _same(d, _dual_v2(m, ctx, d, blob=False, blob_len=L), want,
+          "DualProofV2 metadata without a blob")
+
+
+@pytest.mark.parametrize("k", [1, 257])
+def test_dual_v2_offsets_not_from_zero(m, ctx, dual_v2_full, k):
+    """Rows [k, n) as a slice of the whole batch: incl_off + k and cons_off + k
+    (first entries above 0), the term arrays whole, the per-proof arrays
+    advanced.  k = 257 starts the slice past a 256-lane workgroup edge."""
+    c = U.dual_v2_rows()
+    assert c.n > 257 + 256 and c.incl_off[k] > 0 and c.cons_off[k] > 0
+    st = _dual_v2(m, ctx, c, k=k)
+    _same(c, st, dual_v2_full[k:], "DualProofV2 status of rows [%d, n)" % k, np.arange(k, c.n))
+
+
+def test_dual_v2_array_vs_wire(m, ctx, orc, dual_v2_full):
+    """The corpus as DualProofV2 messages (DualProofV2ToProto through the
+    protobuf runtime) into mh_verify_dual_proof_v2_pb_batch: the array call's
+    status on every row, as test_gpu_pb_decode._compose composes them -- the
+    decode status where it is not 0, a v0 header's metadata dropped (no row
+    of the corpus has any).  Six messages carry 600 KiB of an unknown field,
+    so that MH_PB_CHUNK_MIB=1 cuts the batch into at least three chunks of
+    different sizes, which reuse one verifier scratch."""
+    import wire
+    from immustore_amd import txlayer
+    from test_gpu_formats import _rec_hdr
+    from test_gpu_pb_decode import tag
+    c = U.dual_v2_rows()
+    assert not ((c.sh["md_len"] > 0) & (c.sh["version"] == 0)).any()
+    assert not ((c.th["md_len"] > 0) & (c.th["version"] == 0)).any()
+    msgs = []
+    for p in range(c.n):
+        M = wire.MSG["DualProofV2"]()
+        M.sourceTxHeader.CopyFrom(wire.tx_header_msg(_rec_hdr(c.sh[p], c.blob))[1])
+        M.targetTxHeader.CopyFrom(wire.tx_header_msg(_rec_hdr(c.th[p], c.blob))[1])
+        M.inclusionProof.extend(x.tobytes() for x in c.incl[int(c.incl_off[p]):int(c.incl_off[p + 1])])
+        M.consistencyProof.extend(x.tobytes() for x in c.cons[int(c.cons_off[p]):int(c.cons_off[p + 1])])
+        msgs.append(M.SerializeToString())
+    pad = 600 << 10
+    ln, v = b"", pad
+    while v >= 0x80:
+        ln += bytes([v & 0x7f | 0x80])
+        v >>= 7
+    for p in np.linspace(0, c.n - 1, 6).astype(int):
+        msgs[p] += tag(20, 2) + ln + bytes([v]) + bytes(pad)
+    dst = txlayer.decode_dual_proof_v2_pb(msgs, ctx=ctx)[0]
+    want = np.where(dst != 0, dst, dual_v2_full)
+    assert set(want.tolist()) == DUAL_V2_STATUSES
+    args = (msgs, c.s, c.t, list(c.sa), list(c.ta))
+    _same(c, txlayer.verify_dual_proof_v2_pb_batch(*args, ctx=ctx), want, "wire vs array, one chunk")
+    assert sum(len(x) for x in msgs) > 3 << 20 and max(len(x) for x in msgs) < 1 << 20
+    old = os.environ.get("MH_PB_CHUNK_MIB")
+    os.environ["MH_PB_CHUNK_MIB"] = "1"
+    try:
+        st = txlayer.verify_dual_proof_v2_pb_batch(*args, ctx=ctx)
+    finally:
+        if old is None:
+            del os.environ["MH_PB_CHUNK_MIB"]
+        else:
+            os.environ["MH_PB_CHUNK_MIB"] = old
+    _same(c, st, want, "wire vs array, 1 MiB chunks")
 
 
 # ------------------------------------------------------------ second stride
