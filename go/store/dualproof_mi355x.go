@@ -224,3 +224,109 @@ func verifyDualProofMessages(msgs [][]byte, src, tgt []uint64,
 	}
 	return ok, nil
 }
+
+// VerifiedGetRequest and VerifiedGetState are the fields of
+// schema.KeyRequest and schema.ImmutableState that verifiedGet reads
+// (client.go:1130-1191), in plain types: pkg/api/schema imports this package,
+// so it cannot be named here.  A caller in pkg/client fills them from kReq.Key
+// / kReq.AtTx and state.TxId / state.TxHash.
+type VerifiedGetRequest struct {
+	Key  []byte // kReq.Key, without the set-key prefix
+	AtTx uint64 // kReq.AtTx
+}
+
+type VerifiedGetState struct {
+	TxID   uint64 // state.TxId; 0: no state yet
+	TxHash []byte // state.TxHash; DigestFromProto: at most 32 bytes count
+}
+
+// VerifyVerifiableEntries is what pkg/client's verifiedGet does with every
+// VerifiableGet answer before the state signature check (client.go:1140-1220)
+// -- proto.Unmarshal into schema.VerifiableEntry, EncodeEntrySpec /
+// EncodeReference, EntrySpecDigestFor, htree.VerifyInclusion, the choice of
+// source and target, store.VerifyDualProof -- for a batch of marshalled answers
+// in one device pass over the clique's GPUs
+// (mh_multi_verify_verifiable_entry_pb_batch): answers, keys and states go up
+// once, one status, one verdict and the new state come back per answer.
+// errs[p] is nil and newStates[p] the state verifiedGet would store, or the
+// error it would return: ErrCorruptedData where the proofs do not verify
+// (client.go:1198) or the answer does not decode, ErrIllegalArguments where Go
+// would dereference a nil part of the answer, ErrUnsupportedTxVersion from
+// EntrySpecDigestFor.  A missing LinearAdvanceProof is verified as it stands:
+// FillMissingLinearAdvanceProof stays with the caller.
+func VerifyVerifiableEntries(answers [][]byte, reqs []VerifiedGetRequest,
+	states []VerifiedGetState) (newStates []VerifiedGetState, errs []error, err error) {
+	n := len(answers)
+	if len(reqs) != n || len(states) != n {
+		return nil, nil, ErrIllegalArguments
+	}
+	if n == 0 {
+		return nil, nil, nil
+	}
+	buf, off := packDualProofMessages(answers)
+	keyOff := make([]uint64, n+1)
+	atTx := make([]uint64, n)
+	stateTx := make([]uint64, n)
+	stateAlh := make([][sha256.Size]byte, n)
+	total := 0
+	for _, r := range reqs {
+		total += len(r.Key)
+	}
+	keys := make([]byte, 0, total+1)
+	for p := range reqs {
+		keys = append(keys, reqs[p].Key...)
+		keyOff[p+1] = uint64(len(keys))
+		atTx[p], stateTx[p] = reqs[p].AtTx, states[p].TxID
+		copy(stateAlh[p][:], states[p].TxHash) // DigestFromProto (database_protoconv.go:293-297)
+	}
+	keys = append(keys, 0)
+	status := make([]int32, n)
+	verdict := make([]uint8, n)
+	newTx := make([]uint64, n)
+	newAlh := make([][sha256.Size]byte, n)
+	// the batch struct lives in C memory: cgo forbids passing a Go pointer to
+	// Go memory that itself holds Go pointers
+	b := (*C.mh_verified_get_batch)(C.calloc(1, C.size_t(unsafe.Sizeof(C.mh_verified_get_batch{}))))
+	if b == nil {
+		return nil, nil, ErrIllegalState
+	}
+	defer C.free(unsafe.Pointer(b))
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	for _, ptr := range []unsafe.Pointer{unsafe.Pointer(&buf[0]), unsafe.Pointer(&off[0]),
+		unsafe.Pointer(&keys[0]), unsafe.Pointer(&keyOff[0]), unsafe.Pointer(&atTx[0]),
+		unsafe.Pointer(&stateTx[0]), unsafe.Pointer(&stateAlh[0][0])} {
+		pin.Pin(ptr)
+	}
+	b.n = C.uint64_t(n)
+	b.msgs, b.msg_off = (*C.uint8_t)(unsafe.Pointer(&buf[0])), (*C.uint64_t)(unsafe.Pointer(&off[0]))
+	b.keys, b.key_off = (*C.uint8_t)(unsafe.Pointer(&keys[0])), (*C.uint64_t)(unsafe.Pointer(&keyOff[0]))
+	b.at_tx, b.state_tx = (*C.uint64_t)(unsafe.Pointer(&atTx[0])), (*C.uint64_t)(unsafe.Pointer(&stateTx[0]))
+	b.state_alh = (*C.uint8_t)(unsafe.Pointer(&stateAlh[0][0]))
+	m, e := mi355x.AcquireClique()
+	if e != nil {
+		return nil, nil, e
+	}
+	st := C.mh_multi_verify_verifiable_entry_pb_batch((*C.mh_multi)(m), b,
+		(*C.int32_t)(unsafe.Pointer(&status[0])), (*C.uint8_t)(unsafe.Pointer(&verdict[0])),
+		(*C.uint64_t)(unsafe.Pointer(&newTx[0])), (*C.uint8_t)(unsafe.Pointer(&newAlh[0][0])))
+	mi355x.ReleaseClique(m, int(st))
+	if st != C.MH_OK {
+		return nil, nil, mapErr(st)
+	}
+	newStates = make([]VerifiedGetState, n)
+	errs = make([]error, n)
+	for p := 0; p < n; p++ {
+		switch {
+		case status[p] == C.MH_ERR_UNSUPPORTED_TX_VERSION:
+			errs[p] = ErrUnsupportedTxVersion // immustore.go:90, from EntrySpecDigestFor
+		case status[p] != 0:
+			errs[p] = mapErr(C.int(status[p]))
+		case verdict[p] == 0:
+			errs[p] = ErrCorruptedData // client.go:1198, and verifyDualProof's error
+		default:
+			newStates[p] = VerifiedGetState{TxID: newTx[p], TxHash: append([]byte(nil), newAlh[p][:]...)}
+		}
+	}
+	return newStates, errs, nil
+}

@@ -187,6 +187,7 @@ struct mh_ctx {
     DevBuf s_edge;        // ahtree frontier of a ranged append (64 x 32 B)
     DevBuf s_sort;        // length-class sort of ragged messages (varlen_kernels.hip)
     DevBuf s_tx, s_tree;  // tx layer (capi_tx.hip)
+    DevBuf s_ventry;      // inclusion terms of VerifiableGet answers (capi_entry.hip)
     DevBuf s_txlog;       // raw tx-log bytes of mh_txlog_validate
     DevBuf s_txpatch;     // the same + canonical metadata records (rare)
     DevBuf s_clog;        // mh_txlog_validate_clog's per-record arrays
@@ -505,6 +506,35 @@ struct PbChunkFrame {
         MH_HIP(ensure_chunk_events(c, nch));
         return MH_OK;
     }
+    // groups: consecutive chunks decoded and verified by one set of launches
+    // (group g holds chunks [gcut[g], gcut[g + 1])).  Every kernel of these
+    // calls runs one message per lane, so a launch lasts as long as its
+    // longest message takes one lane (~2.7 MB/s through both decode passes,
+    // measured) however few messages it holds, while a chunk lands at
+    // ~55 GB/s: launching per chunk pays that latency once per chunk for
+    // nothing when messages are long (1 GiB of 44 KB messages, 312 KB the
+    // longest: 1056 ms chunk by chunk, 8 x 115 ms of decode alone).  A group
+    // therefore grows until its bytes take the link as long as its longest
+    // message takes a lane, bytes >= ratio x longest (MH_PB_GROUP_RATIO,
+    // default 16384; 0: every chunk alone): short messages keep the
+    // chunk-by-chunk pipeline, long ones wait for more of the batch.
+    std::vector<int> groups() const {
+        uint64_t ratio = 16384;
+        if (const char *e = getenv("MH_PB_GROUP_RATIO")) ratio = (uint64_t)std::max(0, atoi(e));
+        std::vector<int> gcut{0};
+        for (int k = 0; k < nch;) {
+            uint64_t bytes = 0, lm = 0;
+            int j = k;
+            do {
+                bytes += msg_off[cut[j + 1]] - msg_off[cut[j]];
+                lm = std::max(lm, longest[j]);
+                j++;
+            } while (j < nch && bytes / std::max<uint64_t>(lm, 1) < ratio);
+            gcut.push_back(j);
+            k = j;
+        }
+        return gcut;
+    }
     // chunk 0 carries the per-message arrays whole (offsets, ids, Alh values,
     // sources then targets at d_alh: few large copies -- each copy call costs
     // the DMA engine ~0.1 ms of setup) and the first messages, chunk k its
@@ -669,6 +699,20 @@ int dual_proof_v2_core(hipStream_t st, Timer *tm, uint64_t n, const mh_tx_header
 // nk, Q) device bytes, 256-byte aligned.  Only launches on st: no copy from or
 // to the host, no synchronisation.
 uint64_t dual_proof_v1_scratch_bytes(uint64_t nk, uint64_t Q);
+// The decoders' kernels other translation units launch (pb_decode.hip).
+// DualProof (v1) messages in begin-and-end form: message p is msgs[beg[p] ..
+// end[p]); write = false: status and the kCounts x n counts, write = true: o
+// at its scanned offsets (k_pbd_dual1).
+hipError_t launch_pbd_dual1_range(hipStream_t st, bool write, uint64_t n, const uint8_t *msgs,
+                                  const uint64_t *beg, const uint64_t *end, uint64_t *cnt,
+                                  const Dual1Arrays &o, int32_t *status);
+// VerifiableEntry envelopes (k_pbd_ventry): message p is msgs[msg_off[p] ..
+// msg_off[p + 1]); write = false: status and v.cnt, write = true: the rest of v
+hipError_t launch_pbd_ventry(hipStream_t st, bool write, uint64_t n, const uint8_t *msgs,
+                             const uint64_t *msg_off, const VentryArrays &v, int32_t *status);
+// small read-backs by kernel stores into pinned host memory (out: device view)
+hipError_t launch_put2_host(hipStream_t st, const uint64_t *a, const uint64_t *b, uint64_t *out);
+hipError_t launch_put7_host(hipStream_t st, const uint64_t *so, uint64_t n, uint64_t *out);
 int dual_proof_v1_core(hipStream_t st, Timer *tm, uint64_t nk, const Dual1Arrays &o,
                        const uint64_t *src, const uint64_t *tgt, const uint8_t *src_alh,
                        const uint8_t *tgt_alh, const int32_t *status, uint64_t md_blob_len,

@@ -1184,6 +1184,42 @@ extern "C" int mh_multi_verify_dual_proof_pb_batch(mh_multi *m, uint64_t n, cons
     });
 }
 
+// Whole VerifiableGet answers (verifiedGet, pkg/client/client.go:1119-1234)
+// over n messages, split into K parts of nearly equal message bytes; every
+// per-answer array and the key offsets keep their indexing, so part d is the
+// same batch seen from answer t[d].
+extern "C" int mh_multi_verify_verifiable_entry_pb_batch(mh_multi *m,
+                                                         const mh_verified_get_batch *b,
+                                                         int32_t *status, uint8_t *ok,
+                                                         uint64_t *new_tx, uint8_t *new_alh) {
+    return mh_guard([&]() -> int {
+        if (!m) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (!b || m->K == 1 || b->n < (uint64_t)m->K)
+            return mh_verify_verifiable_entry_pb_batch(m->ctx[0], b, status, ok, new_tx, new_alh);
+        const uint64_t n = b->n;
+        if (!b->msg_off || !b->key_off || !b->at_tx || !b->state_tx || !b->state_alh || !status ||
+            !ok || !new_tx || !new_alh)
+            return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (n > 0x7fffffffull || !monotonic(b->msg_off, n)) return MH_ERR_ILLEGAL_ARGUMENTS;
+        const std::vector<uint64_t> t =
+            split_by_bytes(n, m->K, [&](uint64_t i) { return b->msg_off[i]; });
+        std::lock_guard<std::mutex> lk(m->mu);
+        return per_device(m->K, [&](int d) -> int {
+            const uint64_t lo = t[d], hi = t[d + 1];
+            if (hi == lo) return MH_OK;
+            mh_verified_get_batch part = *b;
+            part.n = hi - lo;
+            part.msg_off += lo;
+            part.key_off += lo;
+            part.at_tx += lo;
+            part.state_tx += lo;
+            part.state_alh += 32 * lo;
+            return mh_verify_verifiable_entry_pb_batch(m->ctx[d], &part, status + lo, ok + lo,
+                                                       new_tx + lo, new_alh + 32 * lo);
+        });
+    });
+}
+
 // precommit's hashing (immustore.go:1620-1632, 2301-2313 -> tx.go:332-355) for
 // a batch of transactions, split into K parts of whole transactions with
 // nearly equal value bytes; part d runs on device d's own commit pipe (made

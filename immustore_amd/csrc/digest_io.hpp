@@ -101,6 +101,75 @@ __device__ inline void sha256_bytes(const uint8_t *p, uint64_t len, int pre, uin
 }
 
 // ============================================================================
+// sha256_bytes with a short register prefix and an optional 32-byte register
+// suffix: SHA256(pre[0:plen] || p[0:len] || suf[0:32]), plen <= 16, pre and
+// suf as big-endian words.  The messages of an EntrySpec digest (client side,
+// verification.go:257-302): the prefixed value or reference, read in place at
+// any alignment, and BE16 mdLen || md || BE16 kLen || 0x00 || key || hVal.
+// One block loop, padding blocks included, so one inlined compression; the
+// loads are guarded to [p, p + len) word by word as in sha256_bytes' last
+// block.  A suffix word is picked from suf[] by compares, not by a dynamic
+// register index (that would go to scratch).
+// ============================================================================
+__device__ __forceinline__ uint32_t be_keep(int64_t v) {  // the first v bytes of a word
+    return v >= 4 ? 0xffffffffu : (v <= 0 ? 0u : (0xffffffffu << (32 - 8 * (int)v)));
+}
+
+template <bool SUF>
+__device__ inline void sha256_seg(const uint32_t pre[4], uint32_t plen, const uint8_t *p,
+                                  uint64_t len, const uint32_t suf[8], uint32_t out[8]) {
+    State s;
+    s.init();
+    const uint64_t L0 = plen + len, L = L0 + (SUF ? 32 : 0);  // before the suffix, in all
+    const uint8_t *q = p - plen;                              // virtual byte 0 address
+    const uint32_t al = (uint32_t)((uintptr_t)q & 3), sel = be_sel(al);
+    const uint32_t *base = reinterpret_cast<const uint32_t *>(q - al);
+    const uint8_t *end = p + len;
+    const uint64_t nblk = (L + 9 + 63) >> 6;  // 0x80 and the 8 length bytes included
+    for (uint64_t b = 0; b < nblk; b++) {
+        const uint32_t *qq = base + b * 16;
+        uint32_t d[17], w[16];
+#pragma unroll
+        for (int j = 0; j < 17; j++) d[j] = ld_guard(qq + j, p, end);
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            const int64_t o = (int64_t)(b * 64) + 4 * j;  // this word's message offset
+            uint32_t x = __builtin_amdgcn_perm(d[j + 1], d[j], sel);
+            if (j < 4) {
+                const uint32_t m = be_keep(b == 0 ? (int64_t)plen - 4 * j : 0);
+                x = (pre[j] & m) | (x & ~m);
+            }
+            x &= be_keep((int64_t)L0 - o);
+            if (SUF) {
+                const int64_t t = o - (int64_t)L0;  // the suffix byte this word starts at
+                if (t > -4 && t < 32) {
+                    const int tw = (int)(t >> 2);
+                    const uint32_t sh = 8 * ((uint32_t)t & 3);
+                    uint32_t hi = 0, lo = 0;
+#pragma unroll
+                    for (int k = 0; k < 8; k++) {
+                        hi = tw == k ? suf[k] : hi;
+                        lo = tw + 1 == k ? suf[k] : lo;
+                    }
+                    x |= sh ? (hi << sh) | (lo >> (32 - sh)) : hi;
+                }
+            }
+            const int64_t v = (int64_t)L - o;  // message bytes in this word
+            x &= be_keep(v);
+            if (v >= 0 && v < 4) x |= 0x80u << (24 - 8 * (int)v);
+            w[j] = x;
+        }
+        if (b == nblk - 1) {
+            w[14] = (uint32_t)((L * 8) >> 32);
+            w[15] = (uint32_t)(L * 8);
+        }
+        compress(s, w);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) out[j] = s.h[j];
+}
+
+// ============================================================================
 // SHA-256 of p[0:la] || p[la+12 : la+44]: an entry-digest message read in
 // place from a raw tx-log entry record (BE16 mdLen | md | BE16 kLen | key |
 // BE32 vLen | BE64 vOff | hVal, tx.go:520-588), skipping the 12 bytes of

@@ -294,6 +294,52 @@ hipError_t launch_dp1_verdict(hipStream_t st, Timer *tm, uint64_t n, const Dp1Op
                               const Dp1Results &r, const uint8_t *has_lin, const uint64_t *first,
                               uint8_t *ok);
 
+// ---- whole VerifiableGet answers (client.go:1119-1234) over device arrays
+// What the envelope pass (k_pbd_ventry, pb_decode.hip) leaves per message of
+// a group of nk: the size pass fills cnt (the inclusion terms, then the bytes
+// of a DualProof that has to be concatenated: cat_all ? every DualProof : one
+// that occurs more than once), the write pass info, the terms at term_off,
+// the concatenations at cat + cat_off, and the DualProof range of every
+// message as [dual_beg, dual_end) relative to the msgs pointer -- in place, or
+// inside cat, which must therefore lie in the allocation msgs points into.
+struct VentryArrays {
+    mh_verifiable_entry_info *info;
+    uint64_t *cnt;                        // 2 x nk
+    const uint64_t *term_off, *cat_off;   // nk + 1 each
+    uint8_t *terms, *cat;
+    uint64_t *dual_beg, *dual_end;        // nk each
+    int cat_all;
+};
+// The hashing of verifiedGet, one answer per lane (k_ventry_verify,
+// ventry_kernels.hip): value hash, EntrySpecDigest, htree.VerifyInclusion
+// against the Eh of the decoded header that is the entry's tx, that header's
+// Alh; writes the arguments of dual_proof_v1_core.  keys biased like msgs
+// (keys + key_off[p] is answer p's key); hdrs: o's headers and metadata after
+// the DualProof write pass; alh_msg: nk x kTxInnerStride bytes of scratch.
+struct VentryVerify {
+    const uint8_t *msgs, *keys;
+    const uint64_t *key_off, *at_tx, *state_tx;
+    const uint8_t *state_alh;
+    const int32_t *status;  // the envelope pass's
+    const mh_verifiable_entry_info *info;
+    const uint64_t *term_off;
+    const uint8_t *terms;
+    const mh_tx_header *src_hdr, *tgt_hdr;
+    const uint8_t *md_blob;
+    uint8_t *alh_msg;
+    uint64_t *src, *tgt;         // out: VerifyDualProof's ids
+    uint8_t *src_alh, *tgt_alh;  // out: and Alh values, nk x 32 each
+    uint8_t *incl_ok;            // out: inclusion holds and the header could be hashed
+};
+hipError_t launch_ventry_verify(hipStream_t st, Timer *tm, uint64_t nk, const VentryVerify &v);
+// ok = status OK && incl_ok && (state_tx == 0 || dual_ok); new_tx / new_alh =
+// tgt / tgt_alh where ok, zeros elsewhere
+hipError_t launch_ventry_verdict(hipStream_t st, Timer *tm, uint64_t nk, const int32_t *status,
+                                 const uint64_t *state_tx, const uint8_t *incl_ok,
+                                 const uint8_t *dual_ok, const uint64_t *tgt,
+                                 const uint8_t *tgt_alh, uint8_t *ok, uint64_t *new_tx,
+                                 uint8_t *new_alh);
+
 __device__ __forceinline__ void copy32_a8(uint8_t *d, const uint8_t *s) {  // both 8-byte aligned
     const uint2 *a = (const uint2 *)s;
     uint2 *b = (uint2 *)d;

@@ -10,6 +10,8 @@
 //   InclusionProofFromProto  :123-129                    schema.proto:534-545
 //   DualProofFromProto (v1)  :213-224, LinearProofFromProto :264-270,
 //   LinearAdvanceProofFromProto :272-287                 schema.proto:388-434
+//   proto.Unmarshal into schema.VerifiableEntry (a VerifiableGet answer, as
+//   pkg/client/client.go:1140-1175 reads it)  schema.proto:208-246, 451-508
 //
 // proto3 wire format as protobuf-go's Unmarshal reads it: fields in any
 // order; a scalar or bytes field seen twice keeps the last value; an embedded
@@ -367,12 +369,16 @@ __global__ __launch_bounds__(256) void k_pbd_incl(uint64_t n, const uint8_t *__r
 template <bool WRITE>
 __global__ __launch_bounds__(256) void k_pbd_dual1(uint64_t n, const uint8_t *__restrict__ msgs,
                                                    const uint64_t *__restrict__ msg_off,
+                                                   const uint64_t *__restrict__ msg_end,
                                                    uint64_t *__restrict__ cnt,  // kCounts x n
                                                    Dual1Arrays o, int32_t *__restrict__ status) {
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
     if (WRITE && p == 0) o.qoff[o.off[kQ][n]] = o.off[kQT][n];  // the nested proofs' closing offset
-    const uint64_t o0 = msg_off[p], o1 = msg_off[p + 1] >= o0 ? msg_off[p + 1] : o0;
+    // message p is [msg_off[p], msg_off[p + 1]), or, begin-and-end form (the
+    // DualProof ranges k_pbd_ventry located), [msg_off[p], msg_end[p])
+    const uint64_t o0 = msg_off[p], oe = msg_end ? msg_end[p] : msg_off[p + 1];
+    const uint64_t o1 = oe >= o0 ? oe : o0;
     const bool corrupt = WRITE && status[p] == MH_ERR_CORRUPTED_DATA;
     mh_tx_header *hs = WRITE ? o.src_hdr + p : nullptr, *ht = WRITE ? o.tgt_hdr + p : nullptr;
     if (WRITE) {
@@ -497,6 +503,234 @@ __global__ __launch_bounds__(256) void k_pbd_dual1(uint64_t n, const uint8_t *__
     if (lt) md_write(mt, o.md_blob + m0 + ls);
 }
 
+// ---------------------------------------------------------------- VerifiableEntry
+// proto.Unmarshal into schema.VerifiableEntry (schema.proto:208-246, 277-293,
+// 344-434, 451-508, 534-545) as pkg/client reads a VerifiableGet answer
+// (client.go:1140-1175): the whole closure of the message is validated --
+// Go unmarshals Tx.entries / kvEntries / zEntries and the signature too, and a
+// malformed field there fails the answer -- and the fields verifiedGet reads
+// are located.  A schema table (message -> field -> kind, child message) and
+// an explicit stack of enclosing messages replace one hand-written loop per
+// message type; the stack lives in LDS (8 levels x 256 lanes: a dynamically
+// indexed local array would go to scratch).
+enum : uint32_t {
+    vVE = 0, vEntry, vRef, vKvmd, vExp, vVtx, vTx, vHdr, vTxmd, vTxEntry, vZEntry, vSig, vDual,
+    vLin, vAdv, vIncl, vMsgs
+};
+// field kinds: 0 unknown, fV varint, fB bytes, f8 fixed64, fM + child message
+enum : uint8_t { fV = 1, fB = 2, f8 = 3, fM = 16 };
+constexpr uint32_t kVeFields = 10;  // field numbers 1..9
+__device__ __constant__ static const uint8_t kVeSchema[vMsgs][kVeFields] = {
+    /* VerifiableEntry    */ {0, fM + vEntry, fM + vVtx, fM + vIncl, 0, 0, 0, 0, 0, 0},
+    /* Entry              */ {0, fV, fB, fB, fM + vRef, fM + vKvmd, fV, fV, 0, 0},
+    /* Reference          */ {0, fV, fB, fV, fM + vKvmd, fV, 0, 0, 0, 0},
+    /* KVMetadata         */ {0, fV, fM + vExp, fV, 0, 0, 0, 0, 0, 0},
+    /* Expiration         */ {0, fV, 0, 0, 0, 0, 0, 0, 0, 0},
+    /* VerifiableTx       */ {0, fM + vTx, fM + vDual, fM + vSig, 0, 0, 0, 0, 0, 0},
+    /* Tx                 */ {0, fM + vHdr, fM + vTxEntry, fM + vEntry, fM + vZEntry, 0, 0, 0, 0, 0},
+    /* TxHeader           */ {0, fV, fB, fV, fV, fB, fV, fB, fV, fM + vTxmd},
+    /* TxMetadata         */ {0, fV, fB, 0, 0, 0, 0, 0, 0, 0},
+    /* TxEntry            */ {0, fB, fB, fV, fM + vKvmd, fB, 0, 0, 0, 0},
+    /* ZEntry             */ {0, fB, fB, fM + vEntry, f8, fV, 0, 0, 0, 0},
+    /* Signature          */ {0, fB, fB, 0, 0, 0, 0, 0, 0, 0},
+    /* DualProof          */ {0, fM + vHdr, fM + vHdr, fB, fB, fB, fB, fM + vLin, fM + vAdv, 0},
+    /* LinearProof        */ {0, fV, fV, fB, 0, 0, 0, 0, 0, 0},
+    /* LinearAdvanceProof */ {0, fB, fM + vIncl, 0, 0, 0, 0, 0, 0, 0},
+    /* InclusionProof     */ {0, fV, fV, fB, 0, 0, 0, 0, 0, 0},
+};
+// What a message is to verifiedGet: only the answer's own entry, reference,
+// metadata, tx header, dual proof and inclusion proof are read; the same
+// message types below Tx.kvEntries / zEntries are validated and nothing more.
+enum : uint32_t {
+    rNone = 0, rRoot, rEntry, rRef, rEmd, rRmd, rEexp, rRexp, rVtx, rTx, rHdr, rDual, rIncl
+};
+__device__ __forceinline__ uint32_t ve_child_role(uint32_t role, uint32_t f) {
+    switch (role * 16 + f) {
+    case rRoot * 16 + 1: return rEntry;
+    case rRoot * 16 + 2: return rVtx;
+    case rRoot * 16 + 3: return rIncl;
+    case rEntry * 16 + 4: return rRef;
+    case rEntry * 16 + 5: return rEmd;
+    case rRef * 16 + 4: return rRmd;
+    case rEmd * 16 + 2: return rEexp;
+    case rRmd * 16 + 2: return rRexp;
+    case rVtx * 16 + 1: return rTx;
+    case rVtx * 16 + 2: return rDual;
+    case rTx * 16 + 1: return rHdr;
+    default: return rNone;
+    }
+}
+enum : uint32_t {  // what was seen (sub-messages) and the metadata flags
+    hEntry = 1u << 0, hVtx = 1u << 1, hIncl = 1u << 2, hRef = 1u << 3, hTx = 1u << 4,
+    hHdr = 1u << 5, hDual = 1u << 6, hDs = 1u << 7, hDt = 1u << 8, hLin = 1u << 9,
+    eDel = 1u << 10, eExp = 1u << 11, eNix = 1u << 12, rDel = 1u << 13, rExp = 1u << 14,
+    rNix = 1u << 15
+};
+constexpr int kVeDepth = 8;  // VerifiableEntry > VerifiableTx > Tx > ZEntry > Entry > Reference
+                             // > KVMetadata > Expiration: 7 messages below the root
+
+// One VerifiableEntry per lane.  WRITE = false: validate, status, count the
+// inclusion terms and the DualProof bytes to concatenate; WRITE = true: info,
+// terms, concatenations and the DualProof range.  Every read goes through the
+// reader of the innermost open message, whose end never exceeds its parent's:
+// nothing is read outside [msg_off[p], msg_off[p + 1]) whatever the lengths
+// inside claim (DigestFromProto's aligned read of a term may touch up to 3
+// bytes beside it, as in the other decoders).
+template <bool WRITE>
+__global__ __launch_bounds__(256) void k_pbd_ventry(uint64_t n, const uint8_t *__restrict__ msgs,
+                                                    const uint64_t *__restrict__ msg_off,
+                                                    VentryArrays v, int32_t *__restrict__ status) {
+    __shared__ uint64_t stk[kVeDepth * 256];
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const uint64_t o0 = msg_off[p], o1 = msg_off[p + 1] >= o0 ? msg_off[p + 1] : o0;
+    // the write pass re-reads only what the first pass gave MH_OK
+    const bool skip = WRITE && status[p] != MH_OK;
+    const uint8_t *base = msgs + o0;
+    PbIn in{base, skip ? base : msgs + o1};
+    uint32_t msg = vVE, role = rRoot, depth = 0, seen = 0;
+    uint64_t etx = 0, rtx = 0, rat = 0, eexp = 0, rexp = 0, lf = 0, wd = 0, kt = 0;
+    const uint8_t *kb = base, *vb = base;
+    uint64_t kl = 0, vl = 0;
+    int32_t ver = 0;
+    uint64_t ndual = 0, dlen = 0, dbeg = 0, cpos = 0;
+    const uint64_t c0 = WRITE ? v.cat_off[p] : 0, clen = WRITE ? v.cat_off[p + 1] - c0 : 0;
+    uint8_t *terms = WRITE ? v.terms + 32 * v.term_off[p] : nullptr;
+    bool ok = true;
+    for (;;) {
+        if (in.p == in.end) {  // the innermost message is read: back to its parent
+            if (depth == 0) break;
+            const uint64_t x = stk[--depth * 256 + threadIdx.x];
+            in.end = base + (x & 0xffffffffffull);
+            msg = (uint32_t)(x >> 40) & 0xff;
+            role = (uint32_t)(x >> 48);
+            continue;
+        }
+        uint32_t f, wt;
+        if (!(ok = in.key(f, wt))) break;
+        const uint32_t kind = f < kVeFields ? kVeSchema[msg][f] : 0;
+        if (kind == fV && wt == 0) {
+            uint64_t x;
+            if (!(ok = in.varint(x))) break;
+            const uint32_t b = x != 0;  // protowire.DecodeBool
+            switch (role * 16 + f) {
+            case rEntry * 16 + 1: etx = x; break;
+            case rRef * 16 + 1: rtx = x; break;
+            case rRef * 16 + 3: rat = x; break;
+            case rEmd * 16 + 1: seen = (seen & ~eDel) | (b ? eDel : 0); break;
+            case rEmd * 16 + 3: seen = (seen & ~eNix) | (b ? eNix : 0); break;
+            case rRmd * 16 + 1: seen = (seen & ~rDel) | (b ? rDel : 0); break;
+            case rRmd * 16 + 3: seen = (seen & ~rNix) | (b ? rNix : 0); break;
+            case rEexp * 16 + 1: eexp = x; break;
+            case rRexp * 16 + 1: rexp = x; break;
+            case rHdr * 16 + 8: ver = (int32_t)(uint32_t)x; break;  // int32: the low 32 bits
+            case rIncl * 16 + 1: lf = (uint64_t)(int64_t)(int32_t)(uint32_t)x; break;
+            case rIncl * 16 + 2: wd = (uint64_t)(int64_t)(int32_t)(uint32_t)x; break;
+            default: break;
+            }
+        } else if (kind == fB && wt == 2) {
+            const uint8_t *b;
+            uint64_t bl;
+            if (!(ok = in.bytes(b, bl))) break;
+            if (role == rEntry && f == 2) kb = b, kl = bl;
+            else if (role == rEntry && f == 3) vb = b, vl = bl;
+            else if (role == rIncl && f == 3) {
+                if (WRITE) digest_from(b, bl, terms + 32 * kt);
+                kt++;
+            }
+        } else if (kind >= fM && wt == 2) {
+            uint64_t len;
+            if (!(ok = in.varint(len) && len <= (uint64_t)(in.end - in.p) && depth < kVeDepth))
+                break;
+            switch (role * 16 + f) {
+            case rRoot * 16 + 1: seen |= hEntry; break;
+            case rRoot * 16 + 2: seen |= hVtx; break;
+            case rRoot * 16 + 3: seen |= hIncl; break;
+            case rEntry * 16 + 4: seen |= hRef; break;
+            case rEmd * 16 + 2: seen |= eExp; break;
+            case rRmd * 16 + 2: seen |= rExp; break;
+            case rVtx * 16 + 1: seen |= hTx; break;
+            case rTx * 16 + 1: seen |= hHdr; break;
+            case rDual * 16 + 1: seen |= hDs; break;
+            case rDual * 16 + 2: seen |= hDt; break;
+            case rDual * 16 + 7: seen |= hLin; break;
+            case rVtx * 16 + 2:  // one more occurrence of the DualProof
+                seen |= hDual;
+                ndual++;
+                dlen += len;
+                dbeg = (uint64_t)(in.p - msgs);
+                if (WRITE && clen) {
+                    for (uint64_t j = 0; j < len && cpos < clen; j++) v.cat[c0 + cpos++] = in.p[j];
+                }
+                break;
+            default: break;
+            }
+            stk[depth++ * 256 + threadIdx.x] =
+                (uint64_t)(in.end - base) | (uint64_t)msg << 40 | (uint64_t)role << 48;
+            in.end = in.p + len;
+            role = ve_child_role(role, f);
+            msg = kind - fM;
+        } else if (kind == f8 && wt == 1) {
+            if (!(ok = in.skip(8))) break;
+        } else if (!(ok = in.skip_value(f, wt))) {
+            break;
+        }
+    }
+    if (!WRITE) {
+        // Go's order: Unmarshal; the nil dereferences of client.go:1145;
+        // EntrySpecDigestFor; the nil dereferences of :1150-1161 and of
+        // DualProofFromProto (as k_pbd_dual1 reports them)
+        const bool have_hdr = (seen & (hVtx | hTx | hHdr)) == (hVtx | hTx | hHdr);
+        const uint32_t rest = hIncl | hDual | hDs | hDt | hLin | hEntry;
+        const int32_t st = !ok ? MH_ERR_CORRUPTED_DATA
+                           : !have_hdr ? MH_ERR_ILLEGAL_ARGUMENTS
+                           : (ver != 0 && ver != 1) ? MH_ERR_UNSUPPORTED_TX_VERSION
+                           : (seen & rest) != rest ? MH_ERR_ILLEGAL_ARGUMENTS : MH_OK;
+        status[p] = st;
+        v.cnt[p] = st == MH_OK ? kt : 0;
+        v.cnt[n + p] = st == MH_OK && (v.cat_all || ndual > 1) ? dlen : 0;
+        return;
+    }
+    mh_verifiable_entry_info *o = v.info + p;
+    uint2 *z = (uint2 *)o;
+    static_assert(sizeof(mh_verifiable_entry_info) == 96, "info is zeroed in 8-byte words");
+#pragma unroll
+    for (int i = 0; i < 12; i++) z[i] = make_uint2(0, 0);
+    if (skip) {
+        v.dual_beg[p] = v.dual_end[p] = o0;
+        return;
+    }
+    const bool ref = seen & hRef;
+    o->entry_tx = etx;
+    o->ref_tx = rtx;
+    o->ref_at_tx = rat;
+    o->key_pos = (uint64_t)(kb - msgs);
+    o->key_len = kl;
+    o->value_pos = (uint64_t)(vb - msgs);
+    o->value_len = vl;
+    o->leaf = lf;
+    o->width = wd;
+    o->tx_version = ver;
+    o->has_ref = ref;
+    // KVMetadataFromProto + KVMetadata.Bytes() (kv_metadata.go:207-219) of the
+    // metadata EncodeEntrySpec / EncodeReference gets
+    const bool del = seen & (ref ? rDel : eDel), ex = seen & (ref ? rExp : eExp),
+               nix = seen & (ref ? rNix : eNix);
+    const uint64_t at = ref ? rexp : eexp;
+    uint32_t k = 0;
+    if (del) o->md[k++] = 0;
+    if (ex) {
+        o->md[k++] = 1;
+        for (int j = 7; j >= 0; j--) o->md[k++] = (uint8_t)(at >> (8 * j));
+    }
+    if (nix) o->md[k++] = 2;
+    o->md_len = (uint8_t)k;
+    // the DualProof: in place when it occurred once, else its concatenation
+    const uint64_t cb = (uint64_t)(v.cat - msgs) + c0;
+    v.dual_beg[p] = clen ? cb : (ndual == 1 ? dbeg : o0);
+    v.dual_end[p] = clen ? cb + clen : (ndual == 1 ? dbeg + dlen : o0);
+}
+
 // Two device words into pinned host memory by a kernel store: a small
 // read-back without a DMA copy, which would queue behind the large
 // host-to-device chunks in flight on the copy engine.
@@ -520,6 +754,43 @@ __global__ void k_put7_host(const uint64_t *__restrict__ so, uint64_t n, volatil
 }
 
 }  // namespace
+
+hipError_t launch_pbd_dual1_range(hipStream_t st, bool write, uint64_t n, const uint8_t *msgs,
+                                  const uint64_t *beg, const uint64_t *end, uint64_t *cnt,
+                                  const Dual1Arrays &o, int32_t *status) {
+    if (!n) return hipSuccess;
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    if (write)
+        hipLaunchKernelGGL(k_pbd_dual1<true>, dim3(grid), dim3(256), 0, st, n, msgs, beg, end,
+                           nullptr, o, status);
+    else
+        hipLaunchKernelGGL(k_pbd_dual1<false>, dim3(grid), dim3(256), 0, st, n, msgs, beg, end, cnt,
+                           Dual1Arrays{}, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_pbd_ventry(hipStream_t st, bool write, uint64_t n, const uint8_t *msgs,
+                             const uint64_t *msg_off, const VentryArrays &v, int32_t *status) {
+    if (!n) return hipSuccess;
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    if (write)
+        hipLaunchKernelGGL(k_pbd_ventry<true>, dim3(grid), dim3(256), 0, st, n, msgs, msg_off, v,
+                           status);
+    else
+        hipLaunchKernelGGL(k_pbd_ventry<false>, dim3(grid), dim3(256), 0, st, n, msgs, msg_off, v,
+                           status);
+    return hipGetLastError();
+}
+
+hipError_t launch_put2_host(hipStream_t st, const uint64_t *a, const uint64_t *b, uint64_t *out) {
+    hipLaunchKernelGGL(k_put2_host, dim3(1), dim3(64), 0, st, a, b, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_put7_host(hipStream_t st, const uint64_t *so, uint64_t n, uint64_t *out) {
+    hipLaunchKernelGGL(k_put7_host, dim3(1), dim3(64), 0, st, so, n, out);
+    return hipGetLastError();
+}
 
 extern "C" int mh_dual_proof_v2_pb_decode_batch(
     mh_ctx *c, uint64_t n, const uint8_t *msgs, const uint64_t *msg_off, mh_tx_header *src_hdr,
@@ -709,7 +980,7 @@ extern "C" int mh_dual_proof_pb_decode_batch(mh_ctx *c, uint64_t n, const uint8_
         const uint8_t *dmsg = base + b_msg - m0;
         uint64_t *cnt = (uint64_t *)(base + b_cnt), *so = (uint64_t *)(base + b_so);
         hipLaunchKernelGGL(k_pbd_dual1<false>, dim3(grid), dim3(256), 0, st, n, dmsg,
-                           (const uint64_t *)(base + b_off), cnt, Dual1Arrays{},
+                           (const uint64_t *)(base + b_off), nullptr, cnt, Dual1Arrays{},
                            (int32_t *)(base + b_st));
         MH_HIP(hipGetLastError());
         for (int j = 0; j < kCounts; j++) {
@@ -769,7 +1040,8 @@ extern "C" int mh_dual_proof_pb_decode_batch(mh_ctx *c, uint64_t n, const uint8_
         o.lin_src = (uint64_t *)(base + b_ls);
         o.lin_tgt = o.lin_src + n;
         hipLaunchKernelGGL(k_pbd_dual1<true>, dim3(grid), dim3(256), 0, st, n, dmsg,
-                           (const uint64_t *)(base + b_off), nullptr, o, (int32_t *)(base + b_st));
+                           (const uint64_t *)(base + b_off), nullptr, nullptr, o,
+                           (int32_t *)(base + b_st));
         MH_HIP(hipGetLastError());
         const size_t hb = n * sizeof(mh_tx_header);
         MH_HIP(hipMemcpyAsync(out->src_hdr, base + b_h, hb, hipMemcpyDeviceToHost, st));
@@ -913,37 +1185,12 @@ extern "C" int mh_verify_dual_proof_pb_batch(mh_ctx *c, uint64_t n, const uint8_
         if (n == 0) return MH_OK;
         PbChunkFrame F;
         if (int e = F.open(c, n, msgs, msg_off, src, tgt, src_alh, tgt_alh, status && ok)) return e;
-        const std::vector<uint64_t> &cut = F.cut, &longest = F.longest;
+        const std::vector<uint64_t> &cut = F.cut;
         const uint64_t m0 = F.m0, mb = F.mb;
-        const int nch = F.nch;
         hipStream_t st = c->stream;
         Timer *tm = c->tm();
-        // groups: consecutive chunks decoded and verified by one set of
-        // launches.  Every kernel here runs one message per lane, so a launch
-        // lasts as long as its longest message takes one lane (~2.7 MB/s
-        // through both decode passes, measured) however few messages it
-        // holds, while a chunk lands at ~55 GB/s: launching per chunk pays
-        // that latency once per chunk for nothing when messages are long
-        // (1 GiB of 44 KB messages, 312 KB the longest: 1056 ms chunk by
-        // chunk, 8 x 115 ms of decode alone).  A group therefore grows until
-        // its bytes take the link as long as its longest message takes a
-        // lane, bytes >= ratio x longest (MH_PB_GROUP_RATIO, default 16384;
-        // 0: every chunk alone): short messages keep the chunk-by-chunk
-        // pipeline, long ones wait for more of the batch.
-        uint64_t ratio = 16384;
-        if (const char *e = getenv("MH_PB_GROUP_RATIO")) ratio = (uint64_t)std::max(0, atoi(e));
-        std::vector<int> gcut{0};
-        for (int k = 0; k < nch;) {
-            uint64_t bytes = 0, lm = 0;
-            int j = k;
-            do {
-                bytes += msg_off[cut[j + 1]] - msg_off[cut[j]];
-                lm = std::max(lm, longest[j]);
-                j++;
-            } while (j < nch && bytes / std::max<uint64_t>(lm, 1) < ratio);
-            gcut.push_back(j);
-            k = j;
-        }
+        // consecutive chunks decoded and verified by one set of launches
+        const std::vector<int> gcut = F.groups();
         const int ng = (int)gcut.size() - 1;
         uint64_t M = 0;  // proofs of the largest group
         for (int g = 0; g < ng; g++) M = std::max(M, cut[gcut[g + 1]] - cut[gcut[g]]);
@@ -982,7 +1229,7 @@ extern "C" int mh_verify_dual_proof_pb_batch(mh_ctx *c, uint64_t n, const uint8_
             {
                 TimerScope ts(tm, "pbd_dual1_size", st);
                 hipLaunchKernelGGL(k_pbd_dual1<false>, dim3(grid), dim3(256), 0, st, nk, dmsg, doff,
-                                   cnt, Dual1Arrays{}, dst);
+                                   nullptr, cnt, Dual1Arrays{}, dst);
                 MH_HIP(hipGetLastError());
             }
             for (int j = 0; j < kCounts; j++) {
@@ -1028,7 +1275,7 @@ extern "C" int mh_verify_dual_proof_pb_batch(mh_ctx *c, uint64_t n, const uint8_
             {
                 TimerScope ts(tm, "pbd_dual1_write", st);
                 hipLaunchKernelGGL(k_pbd_dual1<true>, dim3(grid), dim3(256), 0, st, nk, dmsg, doff,
-                                   nullptr, o, dst);
+                                   nullptr, nullptr, o, dst);
                 MH_HIP(hipGetLastError());
             }
             // VerifyDualProof (verification.go:127-235)

@@ -612,3 +612,101 @@ def verify_dual_proof_pb_batch(msgs, src, tgt, src_alh, tgt_alh, ctx: Optional[C
                                                    _addr(s_), _addr(t_), _addr(sa), _addr(ta),
                                                    _addr(st), _addr(ok)))
     return st, ok.astype(bool)
+
+
+# ---------------------------------------------------------------- whole VerifiableGet answers
+class _VerifiedGetBatch(C.Structure):
+    """mirror of mh_verified_get_batch (include/immustore_merkle.h)"""
+    _fields_ = [("n", C.c_uint64)] + [(f, C.c_void_p) for f in (
+        "msgs", "msg_off", "keys", "key_off", "at_tx", "state_tx", "state_alh")]
+
+
+VERIFIABLE_ENTRY_INFO = np.dtype([
+    ("entry_tx", "<u8"), ("ref_tx", "<u8"), ("ref_at_tx", "<u8"), ("key_pos", "<u8"),
+    ("key_len", "<u8"), ("value_pos", "<u8"), ("value_len", "<u8"), ("leaf", "<u8"),
+    ("width", "<u8"), ("tx_version", "<i4"), ("has_ref", "u1"), ("md_len", "u1"),
+    ("md", "u1", (11,)), ("pad_", "u1", (7,))])  # mh_verifiable_entry_info
+assert VERIFIABLE_ENTRY_INFO.itemsize == 96
+
+
+class _VerifiableEntryDecoded(C.Structure):
+    """mirror of mh_verifiable_entry_decoded (include/immustore_merkle.h)"""
+    _fields_ = [("info", C.c_void_p), ("incl_off", C.c_void_p), ("incl_terms", C.c_void_p),
+                ("incl_cap", C.c_uint64), ("dual_off", C.c_void_p), ("dual_bytes", C.c_void_p),
+                ("dual_cap", C.c_uint64)]
+
+
+def pack_verified_get_batch(msgs, keys, at_tx, state_tx, state_alh, lead: int = 0):
+    """The arrays of mh_verified_get_batch for a list of answers -> (struct,
+    the arrays it points into: keep them alive during the call).  lead: unused
+    bytes ahead of the first message and key (msg_off[0] = key_off[0] = lead)."""
+    n = len(msgs)
+    assert len(keys) == n
+    off = np.full(n + 1, lead, np.uint64)
+    koff = np.full(n + 1, lead, np.uint64)
+    if n:
+        off[1:] += np.cumsum([len(x) for x in msgs], dtype=np.uint64)
+        koff[1:] += np.cumsum([len(x) for x in keys], dtype=np.uint64)
+    buf = np.frombuffer(b"\xff" * lead + b"".join(msgs) + b"\0", np.uint8)
+    kbuf = np.frombuffer(b"\xff" * lead + b"".join(bytes(k) for k in keys) + b"\0", np.uint8)
+    at = np.ascontiguousarray(at_tx, np.uint64).reshape(-1)
+    stx = np.ascontiguousarray(state_tx, np.uint64).reshape(-1)
+    sa = _d32(state_alh, n)
+    assert at.size == n and stx.size == n
+    keep = (buf, off, kbuf, koff, at, stx, sa)
+    return _VerifiedGetBatch(n, *[_addr(a) for a in keep]), keep
+
+
+def verify_verifiable_entry_pb_batch(msgs, keys, at_tx, state_tx, state_alh,
+                                     ctx: Optional[Context] = None, lead: int = 0):
+    """What pkg/client's verifiedGet does with a VerifiableGet answer before the
+    signature check (client.go:1119-1234), for many answers in one device pass
+    (mh_verify_verifiable_entry_pb_batch): msgs[p] the encoded VerifiableEntry,
+    keys[p] the request key, at_tx[p] kReq.AtTx, (state_tx[p], state_alh[p]) the
+    client's state (tx 0: none yet) -> (status[n] int32, ok[n] bool, new_tx[n],
+    new_alh[n, 32]: the new state where ok, zeros elsewhere)."""
+    n = len(msgs)
+    if n == 0:
+        return (np.zeros(0, np.int32), np.zeros(0, bool), np.zeros(0, np.uint64),
+                np.zeros((0, 32), np.uint8))
+    b, keep = pack_verified_get_batch(msgs, keys, at_tx, state_tx, state_alh, lead)
+    st, ok = np.zeros(n, np.int32), np.zeros(n, np.uint8)
+    ntx, nalh = np.zeros(n, np.uint64), np.zeros((n, 32), np.uint8)
+    N.check(N.load().mh_verify_verifiable_entry_pb_batch(_ctx(ctx).handle, C.byref(b), _addr(st),
+                                                         _addr(ok), _addr(ntx), _addr(nalh)))
+    del keep
+    return st, ok.astype(bool), ntx, nalh
+
+
+def decode_verifiable_entry_pb(msgs, ctx: Optional[Context] = None):
+    """The envelope pass alone (mh_verifiable_entry_pb_decode_batch) ->
+    (status[n], dict: info (VERIFIABLE_ENTRY_INFO records; key_pos / value_pos
+    index buf), buf (the messages back to back), incl_off, incl_terms, dual_off,
+    dual_bytes (the merged DualProof messages, ready for
+    verify_dual_proof_pb_batch))."""
+    n = len(msgs)
+    off = np.zeros(n + 1, np.uint64)
+    if n:
+        off[1:] = np.cumsum([len(x) for x in msgs], dtype=np.uint64)
+    buf = np.frombuffer(b"".join(msgs) + b"\0", np.uint8)
+    a = {"info": np.zeros(max(n, 1), VERIFIABLE_ENTRY_INFO), "buf": buf[:-1],
+         "incl_off": np.zeros(n + 1, np.uint64), "dual_off": np.zeros(n + 1, np.uint64)}
+    st = np.zeros(max(n, 1), np.int32)
+    L, h = N.load(), _ctx(ctx).handle
+
+    def call(icap, dcap):
+        a["incl_terms"] = np.zeros((max(icap, 1), 32), np.uint8)
+        a["dual_bytes"] = np.zeros(max(dcap, 1), np.uint8)
+        d = _VerifiableEntryDecoded(_addr(a["info"]), _addr(a["incl_off"]), _addr(a["incl_terms"]),
+                                    icap, _addr(a["dual_off"]), _addr(a["dual_bytes"]), dcap)
+        return L.mh_verifiable_entry_pb_decode_batch(h, n, _addr(buf), _addr(off), C.byref(d),
+                                                     _addr(st))
+
+    rc = call(0, 0)
+    if rc == N.MH_ERR_BUFFER_TOO_SMALL:  # the size query
+        rc = call(int(a["incl_off"][n]), int(a["dual_off"][n]))
+    N.check(rc)
+    a["info"] = a["info"][:n]
+    a["incl_terms"] = a["incl_terms"][:int(a["incl_off"][n])]
+    a["dual_bytes"] = a["dual_bytes"][:int(a["dual_off"][n])]
+    return st[:n], a

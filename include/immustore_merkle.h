@@ -975,6 +975,127 @@ int mh_verify_dual_proof_pb_batch(mh_ctx *ctx, uint64_t n, const uint8_t *msgs,
                                   const uint64_t *tgt, const uint8_t *src_alh,
                                   const uint8_t *tgt_alh, int32_t *status, uint8_t *ok);
 
+/* ------------------------------------------- whole VerifiableGet answers
+ * What pkg/client does with every VerifiableGet answer (verifiedGet,
+ * pkg/client/client.go:1119-1234) before the state signature check, for n
+ * answers in one device pass: proto.Unmarshal into schema.VerifiableEntry,
+ * EncodeEntrySpec / EncodeReference (pkg/database/meta.go:54-89) with
+ * KVMetadataFromProto (database_protoconv.go:97-113), the value hash and
+ * EntrySpecDigest_v0 / _v1 (embedded/store/verification.go:244-302),
+ * htree.VerifyInclusion against the Eh of the proof header that is the
+ * entry's transaction, the choice of source and target from the client's
+ * state, VerifyDualProof (verification.go:127-235) and the new state.
+ * FillMissingLinearAdvanceProof (a network fetch) stays with the caller, as
+ * for mh_verify_dual_proof_pb_batch; VerifiedSet / VerifiedTxByID /
+ * VerifiedZAdd / SQL VerifyRow are not covered.
+ *
+ * Answer p is the VerifiableEntry message msgs[msg_off[p] .. msg_off[p+1])
+ * for the request key keys[key_off[p] .. key_off[p+1]) (kReq.Key, without
+ * the 0x00 prefix), kReq.AtTx at_tx[p], and the client's state (state_tx[p],
+ * state_alh[32 p]); state_tx 0 means no state yet.  All host memory, pageable
+ * or pinned; msg_off[0] / key_off[0] need not be 0.  Everything goes up once,
+ * through the chunks and groups of mh_verify_dual_proof_pb_batch
+ * (MH_PB_CHUNK_MIB, MH_PB_GROUP_RATIO); only status, ok, new_tx and new_alh
+ * come back.
+ *
+ * status[p], first match, in Go's order:
+ *   MH_ERR_CORRUPTED_DATA          proto.Unmarshal would fail
+ *   MH_ERR_ILLEGAL_ARGUMENTS       verifiableTx, its tx, or the tx's header
+ *                                  absent (nil dereference, client.go:1145)
+ *   MH_ERR_UNSUPPORTED_TX_VERSION  int(Tx.Header.Version) not 0 or 1
+ *   MH_ERR_ILLEGAL_ARGUMENTS       inclusionProof, verifiableTx.dualProof, one
+ *                                  of its headers or its linearProof, or
+ *                                  entry absent
+ *   MH_OK                          otherwise; the verdict is ok[p]
+ * MH_ERR_CORRUPTED_DATA means what protobuf-go means: the whole closure of
+ * VerifiableEntry is validated (Entry, Reference, KVMetadata, Expiration,
+ * VerifiableTx, Tx, TxHeader, TxMetadata, TxEntry, ZEntry, Signature,
+ * DualProof, LinearProof, LinearAdvanceProof, InclusionProof), the parts the
+ * verifier never reads (Tx.entries, Tx.kvEntries, Tx.zEntries, signature)
+ * included.  Merge rule: fields in any order; of a scalar or bytes field the
+ * last occurrence wins; occurrences of an embedded message are merged
+ * (entry, referencedBy, the metadata messages and inclusionProof are walked
+ * occurrence by occurrence, inclusion terms appended); unknown and mistyped
+ * fields and groups are skipped but must be well formed; a 10-byte varint
+ * whose last byte is above 1 is an error.  When verifiableTx.dualProof occurs
+ * more than once the merged DualProof is the parse of the occurrences'
+ * concatenation, in order.
+ *
+ * ok[p] = 1 iff status[p] == MH_OK and verifiedGet returns no error before
+ * the signature check.  With S = state_tx[p]: vTx = at_tx ? at_tx : (the
+ * reference's tx if referencedBy is present, else entry.tx); the EntrySpec is
+ * key 0x00 || kReq.Key, metadata and value 0x00 || entry.value of the entry,
+ * or, for a reference, the reference's metadata and value 0x01 ||
+ * BE64(ref.atTx) || 0x00 || entry.key; KVMetadata bytes 0x00 if deleted,
+ * 0x01 || BE64(expiresAt) if the expiration message is present (an empty one
+ * counts), 0x02 if nonIndexable; the digest is EntrySpecDigest_v1, or _v0
+ * (metadata ignored, not refused) for a version-0 tx header.  If S <= vTx:
+ * eh = the target header's EH, (src, srcAlh, tgt, tgtAlh) = (S, state_alh,
+ * vTx, TargetTxHeader.Alh()); otherwise eh = the source header's EH and
+ * (vTx, SourceTxHeader.Alh(), S, state_alh).  htree.VerifyInclusion(proof,
+ * digest, eh) must hold (leaf / width the wire's int32 sign-extended, Go's
+ * signed walk, as mh_htree_verify_inclusion_batch), and, if S > 0,
+ * VerifyDualProof(proof, src, tgt, srcAlh, tgtAlh) as
+ * mh_verify_dual_proof_pb_batch runs it (v0 header metadata ignored, a header
+ * version above 1 gives ok = 0, a missing LinearAdvanceProof verified as
+ * nil).  new_tx[p] = tgt and new_alh[32 p] = tgtAlh when ok[p] = 1, zeros
+ * otherwise.  n == 0 returns MH_OK; null pointers, a non-monotonic msg_off /
+ * key_off and n above the V2 call's limit return MH_ERR_ILLEGAL_ARGUMENTS. */
+typedef struct mh_verified_get_batch {
+    uint64_t n;
+    const uint8_t *msgs;
+    const uint64_t *msg_off;  /* n + 1 */
+    const uint8_t *keys;
+    const uint64_t *key_off;  /* n + 1 */
+    const uint64_t *at_tx;    /* n: kReq.AtTx */
+    const uint64_t *state_tx; /* n: state.TxId (0: no state yet) */
+    const uint8_t *state_alh; /* n x 32: DigestFromProto(state.TxHash) */
+} mh_verified_get_batch;
+int mh_verify_verifiable_entry_pb_batch(mh_ctx *ctx, const mh_verified_get_batch *b,
+                                        int32_t *status, uint8_t *ok, uint64_t *new_tx,
+                                        uint8_t *new_alh);
+/* The same over the clique's devices, split by message bytes as
+ * mh_multi_verify_dual_proof_pb_batch (context 0 alone when K == 1 or n < K). */
+int mh_multi_verify_verifiable_entry_pb_batch(mh_multi *m, const mh_verified_get_batch *b,
+                                              int32_t *status, uint8_t *ok, uint64_t *new_tx,
+                                              uint8_t *new_alh);
+/* The envelope pass of the call above on its own (proto.Unmarshal into
+ * schema.VerifiableEntry, client.go:1140-1175's reads of it), for composition
+ * with mh_htree_verify_inclusion_batch and mh_verify_dual_proof_pb_batch:
+ * status[p] as above; info[p] (all zero unless status[p] == MH_OK): entry.tx,
+ * the reference's tx / atTx and has_ref, where entry.key / entry.value lie in
+ * msgs (index of the first byte, length; the last occurrence), the
+ * KVMetadata.Bytes() that count (the reference's if has_ref), the tx header's
+ * version, the inclusion proof's leaf / width (int32 sign-extended, 64-bit
+ * pattern); the inclusion terms (32 bytes each, DigestFromProto) at
+ * incl_terms[32 incl_off[p] ..); the merged DualProof message at
+ * dual_bytes[dual_off[p] .. dual_off[p+1]), ready for
+ * mh_verify_dual_proof_pb_batch.  incl_cap (terms) or dual_cap (bytes) short:
+ * the offsets, statuses and info are written and MH_ERR_BUFFER_TOO_SMALL is
+ * returned. */
+typedef struct mh_verifiable_entry_info {
+    uint64_t entry_tx, ref_tx, ref_at_tx;
+    uint64_t key_pos, key_len, value_pos, value_len;
+    uint64_t leaf, width;
+    int32_t tx_version;
+    uint8_t has_ref;
+    uint8_t md_len; /* <= MH_MAX_KV_METADATA_LEN */
+    uint8_t md[MH_MAX_KV_METADATA_LEN];
+    uint8_t pad_[7];
+} mh_verifiable_entry_info; /* 96 bytes */
+typedef struct mh_verifiable_entry_decoded {
+    mh_verifiable_entry_info *info; /* n */
+    uint64_t *incl_off;             /* n + 1 */
+    uint8_t *incl_terms;
+    uint64_t incl_cap;
+    uint64_t *dual_off;             /* n + 1 */
+    uint8_t *dual_bytes;
+    uint64_t dual_cap;
+} mh_verifiable_entry_decoded;
+int mh_verifiable_entry_pb_decode_batch(mh_ctx *ctx, uint64_t n, const uint8_t *msgs,
+                                        const uint64_t *msg_off,
+                                        mh_verifiable_entry_decoded *out, int32_t *status);
+
 int mh_htree_inclusion_proof_pb_decode_batch(mh_ctx *ctx, uint64_t n, const uint8_t *msgs,
                                              const uint64_t *msg_off, uint64_t *leaf,
                                              uint64_t *width, uint64_t *term_off, uint8_t *terms,
