@@ -308,6 +308,200 @@ __device__ __forceinline__ void swap_words(const uint4 r[4], uint32_t w[16]) {
     }
 }
 
+// FAST body of k_entries_fixed (val_len % 128 == 0, 128 <= val_len <=
+// kFixedFastMaxValLen): straight-line code per entry, three bodies of rounds.
+//   value loop     its own inlined compress() site, `two` / `rem` folded, the
+//                  DMA through a buffer descriptor with no VALU per unit, one
+//                  LDS address register
+//   padding block  one inlined compress_kw() site, K+W table from the host
+//   sha_block()    a called routine (sha256_cdna.hpp) for every other block:
+//                  entry digest, leaf, the in-lane nodes of the LPL-leaf
+//                  group and the workgroup-level nodes
+// Every lane of a busy wave runs every block (a lane past its group's
+// entries carries a state nothing reads; its loads are clamped or skipped and
+// its stores skipped), so the entry loop has no lane masks and no selects.
+// The group's leaves wait in a shift register until its in-lane nodes are
+// hashed after the loop.
+// The pointer parameters carry no __restrict__ on purpose: the noalias scopes
+// that inlining makes of them hide the LDS-DMA's write from the value loop's
+// ds_read_b128, and hipcc then drops the s_waitcnt vmcnt(0) between the two
+// (tests/test_gpu_leaf_routines.py fails without it).
+template <int LPL>
+__device__ __forceinline__ void entries_fixed_fast(
+    const uint8_t *vals, uint32_t val_len, const uint8_t *keys, uint32_t key_len, int version,
+    uint64_t n, uint8_t *hvals_out, uint8_t *levels, const LaneLevels &la, int wg_levels,
+    const KWTable &kwt, char *smem) {
+    const int lane = threadIdx.x & 63;
+    // scalar wave index: the LDS destinations of the DMAs stay in SGPRs
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // K+W of the constant padding block from the launcher (pad_block_kw), one
+    // word per lane; read back as wave-uniform LDS broadcasts.
+    uint32_t *kw_lds = reinterpret_cast<uint32_t *>(smem + (kFixedThreads / 64) * kWaveLds);
+    if (threadIdx.x < 64) kw_lds[threadIdx.x] = kwt.kw[threadIdx.x];
+    __syncthreads();
+    MH_WG_PROBE(0);
+    char *lds = smem + wave * kWaveLds;
+    const uint64_t wave_slot0 = ((uint64_t)blockIdx.x * (kFixedThreads / 64) + wave) * 64;
+    const uint64_t first = (wave_slot0 + lane) * LPL;
+    const int c = first < n ? (int)min<uint64_t>(LPL, n - first) : 0;
+    const bool wave_busy = wave_slot0 * LPL < n;  // wave-uniform
+
+    const uint32_t nfull = val_len >> 6;
+    const uint32_t units = nfull >> 1;
+    const int kw4 = key_len >> 2;
+    // The wave's buffer descriptor and the per-entry lane offsets.
+    // Base = the wave's first entry e0; num_records = the bytes of vals from
+    // there (0 for an idle wave, which issues no load), capped at 2^32 - 1.
+    // A lane offset is at most rel * val_len + 112 with rel <= 64 * LPL - 1 <=
+    // 255, the unit offset at most val_len - 128, so voffset + soffset + 16 <=
+    // 256 * val_len <= 2^31 (val_len <= kFixedFastMaxValLen = 2^23): no 32-bit
+    // wrap, and with rel <= lim every load ends at or before (lim + 1) *
+    // val_len = the bytes that remain, i.e. inside num_records.  The inputs
+    // are wave-uniform; readfirstlane tells the compiler so (64-bit products
+    // are formed on the vector side), which keeps the descriptor in SGPRs.
+    const uint64_t e0 = wave_busy ? wave_slot0 * LPL : 0;
+    const uint64_t ents = wave_busy ? n - e0 : 0;  // entries from e0 on, >= 1 when busy
+    const uint32_t lim = ents - 1 < 0xffffffffull ? (uint32_t)(ents - 1) : 0xffffffffu;  // last rel.
+    const uint64_t left = ents * val_len < 0xffffffffull ? ents * val_len : 0xffffffffull;
+    const uint64_t base = (uint64_t)vals + e0 * val_len;
+    const uint64_t base_s =
+        ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32) |
+        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        (void *)base_s, 0, __builtin_amdgcn_readfirstlane((int)(uint32_t)left), 0x00020000);
+    // the lane's LDS address of chunk 0 of block 0, from smem (kWaveLds is a
+    // multiple of 128, so the chunk / block XORs do not touch the wave part)
+    const uint32_t lds_a0 =
+        (uint32_t)wave * kWaveLds + (uint32_t)lane * 128 + ((((uint32_t)lane >> 1) & 7) << 4);
+    uint32_t node[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the lane group's node of level log2(LPL)
+    if (wave_busy) {
+        uint32_t voff[8];
+        uint32_t leaf[LPL][8];  // leaf[k] = leaf k of the group once the loop is done
+        fast_lane_offsets(val_len, lim, LPL, 0, lane, voff);
+        dma_issue_fast(rsrc, lds, voff, 0);
+#pragma unroll 1
+        for (int i = 0; i < LPL; i++) {
+            State s;
+            s.init();
+            // One block per iteration through ONE compress site (a second
+            // site in this loop doubles its code and costs the contended
+            // headline more than the hidden LDS wait returns:
+            // profiles/ab_fixed_loop.txt).  Once block 1's reads have landed
+            // the whole unit is in registers and the next unit's DMA
+            // overwrites the buffer under block 1's rounds; the next entry's
+            // first unit is issued after the loop and lands under the
+            // padding / digest / leaf blocks.
+#pragma unroll 1
+            for (uint32_t bb = 0; bb < nfull; bb++) {
+                uint4 r[4];
+                uint32_t w[16];
+                // one address register: the empty asm keeps the compiler from
+                // holding all eight chunk addresses live across the kernel
+                // (a v_xor each per block instead)
+                uint32_t a = lds_a0;
+                asm volatile("" : "+v"(a));
+                lds_read4(smem, a ^ ((bb & 1) << 6), r);
+                if (bb & 1) {
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    const uint32_t u1 = (bb >> 1) + 1;
+                    if (u1 < units) dma_issue_fast(rsrc, lds, voff, u1 * 128);
+                }
+                swap_words(r, w);
+                compress(s, w);
+                if (bb == 0 && i == 0) MH_WG_PROBE(3);
+            }
+            if (i + 1 < LPL) {
+                fast_lane_offsets(val_len, lim, LPL, i + 1, lane, voff);
+                dma_issue_fast(rsrc, lds, voff, 0);
+            }
+            compress_kw(s, kw_lds);
+            // s holds hVal (immustore.go:1629); TxEntryDigest (tx.go:690-731)
+            const uint64_t idx = first + i;
+            const bool on = i < c;
+            if (on && hvals_out) store_digest(hvals_out + idx * 32, s.h);
+            uint32_t w[16];
+            uint32_t key[5] = {0, 0, 0, 0, 0};
+            const uint32_t *kp = reinterpret_cast<const uint32_t *>(keys + idx * key_len);
+#pragma unroll
+            for (int j = 0; j < 5; j++)
+                if (on && j < kw4) key[j] = bswap(kp[j]);
+            digest_block(version, kw4, key, s.h, w);
+            s.init();
+            sha_block(s, w);
+            // leaf = SHA256(0x00 || digest)  (htree.go:79-83)
+            w[0] = s.h[0] >> 8;
+#pragma unroll
+            for (int j = 1; j < 8; j++) w[j] = __builtin_amdgcn_alignbit(s.h[j - 1], s.h[j], 8);
+            w[8] = (s.h[7] << 24) | 0x00800000u;
+#pragma unroll
+            for (int j = 9; j < 15; j++) w[j] = 0;
+            w[15] = 33u * 8u;
+            s.init();
+            sha_block(s, w);
+            if (on) store_digest(levels + idx * 32, s.h);  // level 0 offset is 0
+#pragma unroll
+            for (int k = 0; k + 1 < LPL; k++) copy8(leaf[k], leaf[k + 1]);
+            copy8(leaf[LPL - 1], s.h);
+        }
+        // in-lane nodes of the aligned group: its valid count c decides
+        // hashing vs promotion exactly as htree.go:91-104
+        copy8(node, leaf[0]);
+        if constexpr (LPL >= 2) {
+            if (c >= 2) node_hash_call(leaf[0], leaf[1], node);
+            if (c > 0) store_node(levels, la, 1, first >> 1, node);
+        }
+        if constexpr (LPL == 4) {
+            if (c >= 3) {
+                uint32_t rgt[8];
+                copy8(rgt, leaf[2]);
+                if (c == 4) node_hash_call(leaf[2], leaf[LPL - 1], rgt);
+                store_node(levels, la, 1, (first >> 1) + 1, rgt);
+                node_hash_call(node, rgt, node);
+            }
+            if (c > 0) store_node(levels, la, 2, first >> 2, node);
+        }
+    }  // wave_busy
+
+    // -------------------------------------------------------- workgroup subtree
+    // The workgroup's 256 lane-group nodes (level L0 = log2 LPL) are reduced
+    // in LDS to up to 8 more levels (htree.go:85-110), writing every level.
+    constexpr int L0 = Log2<LPL>::v;
+    MH_WG_PROBE(1);
+    if (wg_levels == 0) return;  // launch-uniform
+    const int t = threadIdx.x;
+    uint32_t(*buf)[kFixedThreads][9] = reinterpret_cast<uint32_t(*)[kFixedThreads][9]>(smem);
+    __syncthreads();  // every wave is done with its staging area
+#pragma unroll
+    for (int j = 0; j < 8; j++) buf[0][t][j] = node[j];
+    int cur = 0;
+#pragma unroll 1
+    for (int st = 1; st <= wg_levels; st++) {
+        __syncthreads();
+        const int active = kFixedThreads >> st;
+        const int l = L0 + st;
+        if (t < active) {
+            const uint64_t q = (uint64_t)blockIdx.x * active + t;
+            if (q < la.width[l]) {
+                uint32_t lft[8], rgt[8], out[8];
+#pragma unroll
+                for (int j = 0; j < 8; j++) lft[j] = buf[cur][2 * t][j];
+                if (2 * q + 1 < la.width[l - 1]) {
+#pragma unroll
+                    for (int j = 0; j < 8; j++) rgt[j] = buf[cur][2 * t + 1][j];
+                    node_hash_call(lft, rgt, out);
+                } else {
+                    copy8(out, lft);
+                }
+                store_digest(levels + (la.off[l] + q) * 32, out);
+#pragma unroll
+                for (int j = 0; j < 8; j++) buf[cur ^ 1][t][j] = out[j];
+            }
+        }
+        cur ^= 1;
+    }
+    MH_WG_PROBE(2);
+}
+
 // Per-lane work is a uniform sequence of SHA-256 compressions driven by a
 // small state machine with ONE generic compress() call site (plus one
 // compress_kw for the constant padding block): value blocks -> padding ->
@@ -316,28 +510,27 @@ __device__ __forceinline__ void swap_words(const uint4 r[4], uint32_t w[16]) {
 // 64 round constants of only one inlined compression live in SGPRs.
 enum : int { OP_VALUE = 0, OP_TAIL, OP_DIGEST, OP_LEAF, OP_NODE1, OP_NODE2 };
 
-// FAST (val_len % 128 == 0, 128 <= val_len <= kFixedFastMaxValLen): the value
-// loop with `two` / `rem` folded, the DMA through a buffer descriptor with no
-// VALU per unit, one LDS address register, every lane compressing (a lane
-// past its group's entries carries a state nothing reads), and the padding
-// block's K+W table from the host (kwt).
+//
+// This state machine is the general instantiation (FAST = false: any val_len
+// entries_fixed_supported() accepts, kwt unused); FAST = true is
+// entries_fixed_fast() above.
 template <int LPL, bool FAST>
 __global__ __launch_bounds__(kFixedThreads) void k_entries_fixed(
     const uint8_t *__restrict__ vals, uint32_t val_len, const uint8_t *__restrict__ keys,
     uint32_t key_len, int version, uint64_t n, uint8_t *__restrict__ hvals_out,
     uint8_t *__restrict__ levels, LaneLevels la, int wg_levels, KWTable kwt) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    if constexpr (FAST) {
+        entries_fixed_fast<LPL>(vals, val_len, keys, key_len, version, n, hvals_out, levels, la,
+                                wg_levels, kwt, smem);
+        return;
+    }
     const int lane = threadIdx.x & 63;
-    int wave = threadIdx.x >> 6;
-    // scalar wave index: the LDS destinations of the DMAs stay in SGPRs
-    if (FAST) wave = __builtin_amdgcn_readfirstlane(wave);
+    const int wave = threadIdx.x >> 6;
     // K+W of the constant padding block (value length % 64 == 0), shared by
     // all waves; read back as wave-uniform LDS broadcasts.
     uint32_t *kw_lds = reinterpret_cast<uint32_t *>(smem + (kFixedThreads / 64) * kWaveLds);
-    if (FAST) {
-        // pad_block_kw(val_len) from the launcher, one word per lane
-        if (threadIdx.x < 64) kw_lds[threadIdx.x] = kwt.kw[threadIdx.x];
-    } else if (threadIdx.x == 0) {
+    if (threadIdx.x == 0) {
         // constant schedule of the padding block: 0x80, zeros, 64-bit bit length
         uint32_t w[16];
 #pragma unroll
@@ -370,39 +563,8 @@ __global__ __launch_bounds__(kFixedThreads) void k_entries_fixed(
     State s;
     s.init();
     uint32_t A[8], B[8], ny7 = 0;
-    // FAST: the wave's buffer descriptor and the per-entry lane offsets.
-    // Base = the wave's first entry e0; num_records = the bytes of vals from
-    // there (0 for an idle wave, which issues no load), capped at 2^32 - 1.
-    // A lane offset is at most rel * val_len + 112 with rel <= 64 * LPL - 1 <=
-    // 255, the unit offset at most val_len - 128, so voffset + soffset + 16 <=
-    // 256 * val_len <= 2^31 (val_len <= kFixedFastMaxValLen = 2^23): no 32-bit
-    // wrap, and with rel <= lim every load ends at or before (lim + 1) *
-    // val_len = the bytes that remain, i.e. inside num_records.  The inputs
-    // are wave-uniform; readfirstlane tells the compiler so (64-bit products
-    // are formed on the vector side), which keeps the descriptor in SGPRs.
-    const bool fast_busy = FAST && wave_busy;
-    const uint64_t e0 = fast_busy ? wave_slot0 * LPL : 0;
-    const uint64_t ents = fast_busy ? n - e0 : 0;  // entries from e0 on, >= 1 when busy
-    const uint32_t lim = ents - 1 < 0xffffffffull ? (uint32_t)(ents - 1) : 0xffffffffu;  // last rel.
-    const uint64_t left = ents * val_len < 0xffffffffull ? ents * val_len : 0xffffffffull;
-    const uint64_t base = (uint64_t)vals + e0 * val_len;
-    const uint64_t base_s =
-        ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32) |
-        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)base_s, 0, __builtin_amdgcn_readfirstlane((int)(uint32_t)left), 0x00020000);
-    uint32_t voff[8];
-    // the lane's LDS address of chunk 0 of block 0, from smem (kWaveLds is a
-    // multiple of 128, so the chunk / block XORs do not touch the wave part)
-    const uint32_t lds_a0 =
-        (uint32_t)wave * kWaveLds + (uint32_t)lane * 128 + ((((uint32_t)lane >> 1) & 7) << 4);
     if (wave_busy) {
-    if (FAST) {
-        fast_lane_offsets(val_len, lim, LPL, 0, lane, voff);
-        dma_issue_fast(rsrc, lds, voff, 0);
-    } else {
     if (units) dma_issue(vals, val_len, wave_slot0, LPL, 0, n, 0, nsteps2 > 0, lds, lane);
-    }
 
     int i = 0;         // entry of the lane group (uniform)
     uint32_t b = 0;    // value block (uniform)
@@ -412,42 +574,6 @@ __global__ __launch_bounds__(kFixedThreads) void k_entries_fixed(
     for (;;) {
         const uint64_t idx = first + i;
         bool on = i < c;
-        if (op == OP_VALUE && FAST) {
-            // One block per iteration through ONE compress site (a second
-            // site in this loop doubles its code and costs the contended
-            // headline more than the hidden LDS wait returns:
-            // profiles/ab_fixed_loop.txt).  Once block 1's reads have landed
-            // the whole unit is in registers and the next unit's DMA
-            // overwrites the buffer under block 1's rounds; the next entry's
-            // first unit is issued after the loop and lands under the
-            // padding / digest / leaf blocks.
-#pragma unroll 1
-            for (uint32_t bb = 0; bb < nfull; bb++) {
-                uint4 r[4];
-                uint32_t w[16];
-                // one address register: the empty asm keeps the compiler from
-                // holding all eight chunk addresses live across the kernel
-                // (a v_xor each per block instead)
-                uint32_t a = lds_a0;
-                asm volatile("" : "+v"(a));
-                lds_read4(smem, a ^ ((bb & 1) << 6), r);
-                if (bb & 1) {
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    const uint32_t u1 = (bb >> 1) + 1;
-                    if (u1 < units) dma_issue_fast(rsrc, lds, voff, u1 * 128);
-                }
-                swap_words(r, w);
-                compress(s, w);
-                if (bb == 0 && i == 0) MH_WG_PROBE(3);
-            }
-            if (i + 1 < LPL) {
-                fast_lane_offsets(val_len, lim, LPL, i + 1, lane, voff);
-                dma_issue_fast(rsrc, lds, voff, 0);
-            }
-            if (on) compress_kw(s, kw_lds);
-            op = OP_DIGEST;
-            continue;
-        }
         if (op == OP_VALUE) {
             // tight loop over the value's full blocks: its own compress site,
             // no state-machine dispatch per block

@@ -192,6 +192,63 @@ __device__ __forceinline__ void node_hash(const uint32_t l[8], const uint32_t r[
 }
 
 // ---------------------------------------------------------------------------
+// One compression as a CALLED routine: state and message words go in and the
+// new state comes back by value in VGPRs (vector types, so the calling
+// convention keeps all 24 + 8 words in registers; the routine touches no
+// memory).  A kernel that compresses at many places outside its hot loop
+// calls this instead of inlining ~11 KB of rounds per place.
+typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+
+static __device__ __attribute__((noinline)) u32x8 sha_block_regs(u32x8 h, u32x16 wv) {
+    State s;
+    uint32_t w[16];
+#pragma unroll
+    for (int j = 0; j < 8; j++) s.h[j] = h[j];
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = wv[j];
+    compress(s, w);
+#pragma unroll
+    for (int j = 0; j < 8; j++) h[j] = s.h[j];
+    return h;
+}
+
+__device__ __forceinline__ void sha_block(State &s, const uint32_t w[16]) {
+    u32x8 h;
+    u32x16 wv;
+#pragma unroll
+    for (int j = 0; j < 8; j++) h[j] = s.h[j];
+#pragma unroll
+    for (int j = 0; j < 16; j++) wv[j] = w[j];
+    h = sha_block_regs(h, wv);
+#pragma unroll
+    for (int j = 0; j < 8; j++) s.h[j] = h[j];
+}
+
+// node = SHA256(0x01 || l || r) through two sha_block calls.
+__device__ __forceinline__ void node_hash_call(const uint32_t l[8], const uint32_t r[8],
+                                               uint32_t out[8]) {
+    uint32_t w[16];
+    w[0] = 0x01000000u | (l[0] >> 8);
+#pragma unroll
+    for (int j = 1; j < 8; j++) w[j] = __builtin_amdgcn_alignbit(l[j - 1], l[j], 8);
+    w[8] = __builtin_amdgcn_alignbit(l[7], r[0], 8);
+#pragma unroll
+    for (int j = 1; j < 8; j++) w[8 + j] = __builtin_amdgcn_alignbit(r[j - 1], r[j], 8);
+    const uint32_t r7 = r[7];
+    State s;
+    s.init();
+    sha_block(s, w);
+    w[0] = (r7 << 24) | 0x00800000u;
+#pragma unroll
+    for (int j = 1; j < 15; j++) w[j] = 0;
+    w[15] = 65u * 8u;
+    sha_block(s, w);
+#pragma unroll
+    for (int j = 0; j < 8; j++) out[j] = s.h[j];
+}
+
+// ---------------------------------------------------------------------------
 // Node hashes against a per-workgroup schedule table.
 //
 // The second block of a node hash (65-byte message) is

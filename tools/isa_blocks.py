@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-basic-block instruction mix of one kernel in a gfx950 .s file.
 
-usage: isa_blocks.py file.s mangled_kernel_name [min_instructions]
+usage: isa_blocks.py file.s mangled_function_name [min_instructions]
 """
 import re
 import sys
@@ -15,7 +15,7 @@ def main():
     i = s.find("\n" + name + ":")
     if i < 0:
         sys.exit("kernel not found")
-    j = s.find("s_endpgm", i)
+    j = s.find(".Lfunc_end", i)  # a kernel or a called device routine
     blocks, cur = [], ["entry", []]
     for ln in s[i:j].split("\n")[2:]:
         t = ln.strip()
