@@ -20,6 +20,8 @@ import "C"
 
 import (
 	"crypto/sha256"
+	"encoding/binary"
+	"math"
 	"runtime"
 	"unsafe"
 
@@ -324,6 +326,168 @@ func VerifyVerifiableEntries(answers [][]byte, reqs []VerifiedGetRequest,
 			errs[p] = mapErr(C.int(status[p]))
 		case verdict[p] == 0:
 			errs[p] = ErrCorruptedData // client.go:1198, and verifyDualProof's error
+		default:
+			newStates[p] = VerifiedGetState{TxID: newTx[p], TxHash: append([]byte(nil), newAlh[p][:]...)}
+		}
+	}
+	return newStates, errs, nil
+}
+
+// VerifiedTxKind names the client call a VerifiableTx answer belongs to
+// (MH_VTX_* of immustore_merkle.h, in that order).
+type VerifiedTxKind uint8
+
+const (
+	VerifiedTxSet       VerifiedTxKind = iota // VerifiedSet, client.go:1302
+	VerifiedTxSetAll                          // streamVerifiedSet, streams.go:128
+	VerifiedTxReference                       // VerifiedSetReferenceAt, client.go:1677
+	VerifiedTxZAdd                            // VerifiedZAddAt, client.go:1842
+	VerifiedTxByID                            // VerifiedTxByID, client.go:1527
+)
+
+// VerifiedTxKV is one key / value pair the client sent (schema.KeyValue).
+type VerifiedTxKV struct {
+	Key, Value []byte
+}
+
+// VerifiedTxRequest is what the client sent for one VerifiableTx answer, in
+// plain types (pkg/api/schema imports this package).  Set: one KV.  SetAll:
+// the KVs of the request, in order.  Reference: Key and ReferencedKey, AtTx.
+// ZAdd: Set, Score, Key, AtTx (ZAddRequest).  ByID: Tx, the requested id.
+type VerifiedTxRequest struct {
+	Kind          VerifiedTxKind
+	KVs           []VerifiedTxKV
+	Key           []byte
+	ReferencedKey []byte
+	Set           []byte
+	Score         float64
+	AtTx          uint64
+	Tx            uint64
+}
+
+// wrapZAddReferenceAt is database.WrapZAddReferenceAt (pkg/database/meta.go:
+// 98-117) over database.EncodeKey(key), as VerifiedZAddAt builds the entry's
+// key (client.go:1893-1897): pkg/database cannot be imported from here.
+func wrapZAddReferenceAt(set []byte, score float64, key []byte, atTx uint64) []byte {
+	zKey := make([]byte, 0, 1+8+len(set)+8+8+1+len(key)+8)
+	zKey = append(zKey, 1) // SortedSetKeyPrefix
+	zKey = binary.BigEndian.AppendUint64(zKey, uint64(len(set)))
+	zKey = append(zKey, set...)
+	zKey = binary.BigEndian.AppendUint64(zKey, math.Float64bits(score))
+	zKey = binary.BigEndian.AppendUint64(zKey, uint64(1+len(key)))
+	zKey = append(zKey, 0) // SetKeyPrefix
+	zKey = append(zKey, key...)
+	return binary.BigEndian.AppendUint64(zKey, atTx)
+}
+
+// VerifyVerifiableTxs is what pkg/client does with every schema.VerifiableTx
+// answer before the state signature check -- VerifiedSet (client.go:1337-1391),
+// streamVerifiedSet (streams.go:205-260), VerifiedSetReferenceAt
+// (client.go:1716-1770), VerifiedZAddAt (:1882-1940), VerifiedTxByID
+// (:1554-1583): proto.Unmarshal, TxFromProto with the hash tree of the wire's
+// entries, the inclusion of what the client sent, the rebuilt Eh against the
+// DualProof's target header, the new state's Alh, store.VerifyDualProof -- for
+// a batch of marshalled answers in one device pass over the clique's GPUs
+// (mh_multi_verify_verifiable_tx_pb_batch).  errs[p] is nil and newStates[p]
+// the state the call would store, or the error it would return:
+// ErrCorruptedData where a check fails or the answer does not decode,
+// ErrIllegalArguments where Go would dereference a nil part of the answer,
+// ErrUnsupportedTxVersion from EntrySpecDigestFor.  A missing
+// LinearAdvanceProof is verified as it stands.
+func VerifyVerifiableTxs(answers [][]byte, reqs []VerifiedTxRequest,
+	states []VerifiedGetState) (newStates []VerifiedGetState, errs []error, err error) {
+	n := len(answers)
+	if len(reqs) != n || len(states) != n {
+		return nil, nil, ErrIllegalArguments
+	}
+	if n == 0 {
+		return nil, nil, nil
+	}
+	buf, off := packDualProofMessages(answers)
+	kind := make([]uint8, n)
+	specOff := make([]uint64, n+1)
+	atTx := make([]uint64, n)
+	stateTx := make([]uint64, n)
+	stateAlh := make([][sha256.Size]byte, n)
+	keyOff, valOff := []uint64{0}, []uint64{0}
+	var keys, vals []byte
+	spec := func(k, v []byte) {
+		keys, vals = append(keys, k...), append(vals, v...)
+		keyOff, valOff = append(keyOff, uint64(len(keys))), append(valOff, uint64(len(vals)))
+	}
+	for p := range reqs {
+		r := &reqs[p]
+		kind[p] = uint8(r.Kind)
+		switch r.Kind {
+		case VerifiedTxSet, VerifiedTxSetAll:
+			if len(r.KVs) == 0 || (r.Kind == VerifiedTxSet && len(r.KVs) != 1) {
+				return nil, nil, ErrIllegalArguments
+			}
+			for _, kv := range r.KVs {
+				spec(kv.Key, kv.Value)
+			}
+		case VerifiedTxReference:
+			spec(r.Key, r.ReferencedKey)
+			atTx[p] = r.AtTx
+		case VerifiedTxZAdd:
+			spec(wrapZAddReferenceAt(r.Set, r.Score, r.Key, r.AtTx), nil)
+		case VerifiedTxByID:
+			atTx[p] = r.Tx
+		default:
+			return nil, nil, ErrIllegalArguments
+		}
+		specOff[p+1] = uint64(len(keyOff) - 1)
+		stateTx[p] = states[p].TxID
+		copy(stateAlh[p][:], states[p].TxHash) // DigestFromProto (database_protoconv.go:293-297)
+	}
+	keys, vals = append(keys, 0), append(vals, 0)
+	status := make([]int32, n)
+	verdict := make([]uint8, n)
+	newTx := make([]uint64, n)
+	newAlh := make([][sha256.Size]byte, n)
+	// the batch struct lives in C memory: cgo forbids passing a Go pointer to
+	// Go memory that itself holds Go pointers
+	b := (*C.mh_verified_tx_batch)(C.calloc(1, C.size_t(unsafe.Sizeof(C.mh_verified_tx_batch{}))))
+	if b == nil {
+		return nil, nil, ErrIllegalState
+	}
+	defer C.free(unsafe.Pointer(b))
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	for _, ptr := range []unsafe.Pointer{unsafe.Pointer(&buf[0]), unsafe.Pointer(&off[0]),
+		unsafe.Pointer(&kind[0]), unsafe.Pointer(&specOff[0]), unsafe.Pointer(&keys[0]),
+		unsafe.Pointer(&keyOff[0]), unsafe.Pointer(&vals[0]), unsafe.Pointer(&valOff[0]),
+		unsafe.Pointer(&atTx[0]), unsafe.Pointer(&stateTx[0]), unsafe.Pointer(&stateAlh[0][0])} {
+		pin.Pin(ptr)
+	}
+	b.n = C.uint64_t(n)
+	b.msgs, b.msg_off = (*C.uint8_t)(unsafe.Pointer(&buf[0])), (*C.uint64_t)(unsafe.Pointer(&off[0]))
+	b.kind, b.spec_off = (*C.uint8_t)(unsafe.Pointer(&kind[0])), (*C.uint64_t)(unsafe.Pointer(&specOff[0]))
+	b.keys, b.key_off = (*C.uint8_t)(unsafe.Pointer(&keys[0])), (*C.uint64_t)(unsafe.Pointer(&keyOff[0]))
+	b.vals, b.val_off = (*C.uint8_t)(unsafe.Pointer(&vals[0])), (*C.uint64_t)(unsafe.Pointer(&valOff[0]))
+	b.at_tx, b.state_tx = (*C.uint64_t)(unsafe.Pointer(&atTx[0])), (*C.uint64_t)(unsafe.Pointer(&stateTx[0]))
+	b.state_alh = (*C.uint8_t)(unsafe.Pointer(&stateAlh[0][0]))
+	m, e := mi355x.AcquireClique()
+	if e != nil {
+		return nil, nil, e
+	}
+	st := C.mh_multi_verify_verifiable_tx_pb_batch((*C.mh_multi)(m), b,
+		(*C.int32_t)(unsafe.Pointer(&status[0])), (*C.uint8_t)(unsafe.Pointer(&verdict[0])),
+		(*C.uint64_t)(unsafe.Pointer(&newTx[0])), (*C.uint8_t)(unsafe.Pointer(&newAlh[0][0])), nil)
+	mi355x.ReleaseClique(m, int(st))
+	if st != C.MH_OK {
+		return nil, nil, mapErr(st)
+	}
+	newStates = make([]VerifiedGetState, n)
+	errs = make([]error, n)
+	for p := 0; p < n; p++ {
+		switch {
+		case status[p] == C.MH_ERR_UNSUPPORTED_TX_VERSION:
+			errs[p] = ErrUnsupportedTxVersion // immustore.go:90, from EntrySpecDigestFor
+		case status[p] != 0:
+			errs[p] = mapErr(C.int(status[p]))
+		case verdict[p] == 0:
+			errs[p] = ErrCorruptedData // client.go:1338, 1356, 1363, 1367 and verifyDualProof's error
 		default:
 			newStates[p] = VerifiedGetState{TxID: newTx[p], TxHash: append([]byte(nil), newAlh[p][:]...)}
 		}

@@ -291,6 +291,8 @@ SIGNATURES = {
     "mh_verify_verifiable_entry_pb_batch": (i32, [vp, vp, vp, u8p, vp, u8p]),
     "mh_multi_verify_verifiable_entry_pb_batch": (i32, [vp, vp, vp, u8p, vp, u8p]),
     "mh_verifiable_entry_pb_decode_batch": (i32, [vp, u64, u8p, vp, vp, vp]),
+    "mh_verify_verifiable_tx_pb_batch": (i32, [vp, vp, vp, u8p, vp, u8p, u8p]),
+    "mh_multi_verify_verifiable_tx_pb_batch": (i32, [vp, vp, vp, u8p, vp, u8p, u8p]),
     "mh_verify_document_batch": (i32, [vp, vp, vp, u8p]),
     "mh_commit_queue_new": (i32, [vp, i32, u64, u32, u32, C.POINTER(vp)]),
     "mh_commit_queue_free": (i32, [vp]),

@@ -710,6 +710,10 @@ hipError_t launch_pbd_dual1_range(hipStream_t st, bool write, uint64_t n, const 
 // msg_off[p + 1]); write = false: status and v.cnt, write = true: the rest of v
 hipError_t launch_pbd_ventry(hipStream_t st, bool write, uint64_t n, const uint8_t *msgs,
                              const uint64_t *msg_off, const VentryArrays &v, int32_t *status);
+// VerifiableTx envelopes (k_pbd_vtx): write = false: status, v.live and v.cnt,
+// write = true: the rest of v
+hipError_t launch_pbd_vtx(hipStream_t st, bool write, uint64_t n, const uint8_t *msgs,
+                          const uint64_t *msg_off, const VtxArrays &v, int32_t *status);
 // small read-backs by kernel stores into pinned host memory (out: device view)
 hipError_t launch_put2_host(hipStream_t st, const uint64_t *a, const uint64_t *b, uint64_t *out);
 hipError_t launch_put7_host(hipStream_t st, const uint64_t *so, uint64_t n, uint64_t *out);

@@ -1220,6 +1220,47 @@ extern "C" int mh_multi_verify_verifiable_entry_pb_batch(mh_multi *m,
     });
 }
 
+// Whole VerifiableTx answers (the verified writes and VerifiedTxByID,
+// pkg/client/client.go:1337-1391, 1554-1583) over n messages, split into K
+// parts of nearly equal message bytes; the per-answer arrays advance to the
+// part's first answer, spec_off with them, and key_off / val_off, which the
+// spec numbers index directly, are shared.
+extern "C" int mh_multi_verify_verifiable_tx_pb_batch(mh_multi *m, const mh_verified_tx_batch *b,
+                                                      int32_t *status, uint8_t *ok,
+                                                      uint64_t *new_tx, uint8_t *new_alh,
+                                                      uint8_t *eh_out) {
+    return mh_guard([&]() -> int {
+        if (!m) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (!b || m->K == 1 || b->n < (uint64_t)m->K)
+            return mh_verify_verifiable_tx_pb_batch(m->ctx[0], b, status, ok, new_tx, new_alh,
+                                                    eh_out);
+        const uint64_t n = b->n;
+        if (!b->msg_off || !b->kind || !b->spec_off || !b->key_off || !b->val_off || !b->at_tx ||
+            !b->state_tx || !b->state_alh || !status || !ok || !new_tx || !new_alh)
+            return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (2 * n * (uint64_t)MH_MAX_TX_METADATA_LEN > 0xffffffffull || !monotonic(b->msg_off, n))
+            return MH_ERR_ILLEGAL_ARGUMENTS;
+        const std::vector<uint64_t> t =
+            split_by_bytes(n, m->K, [&](uint64_t i) { return b->msg_off[i]; });
+        std::lock_guard<std::mutex> lk(m->mu);
+        return per_device(m->K, [&](int d) -> int {
+            const uint64_t lo = t[d], hi = t[d + 1];
+            if (hi == lo) return MH_OK;
+            mh_verified_tx_batch part = *b;
+            part.n = hi - lo;
+            part.msg_off += lo;
+            part.kind += lo;
+            part.spec_off += lo;
+            part.at_tx += lo;
+            part.state_tx += lo;
+            part.state_alh += 32 * lo;
+            return mh_verify_verifiable_tx_pb_batch(m->ctx[d], &part, status + lo, ok + lo,
+                                                    new_tx + lo, new_alh + 32 * lo,
+                                                    eh_out ? eh_out + 32 * lo : nullptr);
+        });
+    });
+}
+
 // precommit's hashing (immustore.go:1620-1632, 2301-2313 -> tx.go:332-355) for
 // a batch of transactions, split into K parts of whole transactions with
 // nearly equal value bytes; part d runs on device d's own commit pipe (made

@@ -340,6 +340,68 @@ hipError_t launch_ventry_verdict(hipStream_t st, Timer *tm, uint64_t nk, const i
                                  const uint8_t *tgt_alh, uint8_t *ok, uint64_t *new_tx,
                                  uint8_t *new_alh);
 
+// ---- whole VerifiableTx answers (capi_vtx.hip)
+// One Tx.entries element i < K of a live write answer, at slot spec_off[p] + i
+// (k_pbd_vtx's write pass): DigestFromProto(hValue), where its key lies in the
+// messages, and KVMetadataFromProto(metadata).Bytes().
+struct VtxRec {
+    uint8_t hv[32];
+    uint64_t key_pos, key_len;
+    uint8_t md_len, md[MH_MAX_KV_METADATA_LEN];
+    uint8_t pad_[4];
+};
+static_assert(sizeof(VtxRec) == 64, "records are 16-byte aligned for load_digest");
+// The envelope pass of a group of nk VerifiableTx answers (k_pbd_vtx).  kind /
+// spec_off / state_tx: the group's slices of the caller's arrays (spec_off
+// absolute, recs[0] is slot spec_base = spec_off[0]).  Size pass: status, live,
+// cnt (DualProof bytes to concatenate, as VentryArrays); write pass: hdr (the
+// tx header, its canonical metadata at md_blob + p x MH_MAX_TX_METADATA_LEN),
+// recs, cat and the DualProof range relative to msgs.
+struct VtxArrays {
+    const uint8_t *kind;
+    const uint64_t *spec_off, *state_tx;
+    uint64_t spec_base;
+    uint64_t *cnt;
+    const uint64_t *cat_off;
+    uint8_t *cat;
+    uint64_t *dual_beg, *dual_end;
+    mh_tx_header *hdr;
+    uint8_t *md_blob;
+    uint8_t *live;
+    VtxRec *recs;
+};
+// The per-slot hashing (k_vtx_leaf, k_vtx_spec) and the per-answer step
+// (k_vtx_answer) between the envelope pass and dual_proof_v1_core
+// (ventry_kernels.hip).  Per-answer arrays are the group's slices; key_off /
+// val_off are indexed by the absolute slot, keys / vals biased like msgs; recs
+// / dig / dok / xok start at the group's first slot.
+struct VtxVerify {
+    uint64_t nk;
+    const uint8_t *msgs, *keys, *vals;
+    const uint64_t *spec_off, *key_off, *val_off;
+    const uint8_t *kind;
+    const uint64_t *at_tx, *state_tx;
+    const uint8_t *state_alh;
+    const int32_t *status;
+    const uint8_t *live;
+    const mh_tx_header *hdr;     // tx.header of every answer
+    const uint8_t *md_blob;      // and its metadata
+    const VtxRec *recs;
+    uint8_t *dig;                // d_i, 32 bytes a slot
+    uint8_t *dok, *xok;          // a slot: d_i could be built / x_i == d_{j_i}
+    const uint8_t *roots;        // Eh' of every answer (after build_many_dev)
+    const mh_tx_header *src_hdr, *tgt_hdr;  // the DualProof's, after its write pass
+    const uint8_t *dual_md;
+    uint8_t *alh_msg;            // nk x kTxInnerStride bytes of scratch
+    uint64_t *src, *tgt;         // out: VerifyDualProof's ids
+    uint8_t *src_alh, *tgt_alh;  // out: and Alh values
+    uint8_t *pre_ok;             // out: everything before VerifyDualProof holds
+    uint8_t *eh_out;             // out: Eh' (zeros where it was not reached)
+};
+hipError_t launch_vtx_leaf(hipStream_t st, Timer *tm, uint64_t T, const VtxVerify &v);
+hipError_t launch_vtx_spec(hipStream_t st, Timer *tm, uint64_t T, const VtxVerify &v);
+hipError_t launch_vtx_answer(hipStream_t st, Timer *tm, const VtxVerify &v);
+
 __device__ __forceinline__ void copy32_a8(uint8_t *d, const uint8_t *s) {  // both 8-byte aligned
     const uint2 *a = (const uint2 *)s;
     uint2 *b = (uint2 *)d;

@@ -568,6 +568,22 @@ enum : uint32_t {  // what was seen (sub-messages) and the metadata flags
 };
 constexpr int kVeDepth = 8;  // VerifiableEntry > VerifiableTx > Tx > ZEntry > Entry > Reference
                              // > KVMetadata > Expiration: 7 messages below the root
+// The stack of enclosing messages of the envelope kernels (k_pbd_ventry,
+// k_pbd_vtx): kVeDepth x 256 words of LDS, lane t's level d at stk[d * 256 +
+// t]; a frame is the parent's end (relative to the message, 40 bits), its
+// schema row and its role.
+__device__ __forceinline__ void ve_push(uint64_t *stk, uint32_t &depth, const uint8_t *base,
+                                        const uint8_t *end, uint32_t msg, uint32_t role) {
+    stk[depth++ * 256 + threadIdx.x] =
+        (uint64_t)(end - base) | (uint64_t)msg << 40 | (uint64_t)role << 48;
+}
+__device__ __forceinline__ void ve_pop(const uint64_t *stk, uint32_t &depth, const uint8_t *base,
+                                       const uint8_t *&end, uint32_t &msg, uint32_t &role) {
+    const uint64_t x = stk[--depth * 256 + threadIdx.x];
+    end = base + (x & 0xffffffffffull);
+    msg = (uint32_t)(x >> 40) & 0xff;
+    role = (uint32_t)(x >> 48);
+}
 
 // One VerifiableEntry per lane.  WRITE = false: validate, status, count the
 // inclusion terms and the DualProof bytes to concatenate; WRITE = true: info,
@@ -600,10 +616,7 @@ __global__ __launch_bounds__(256) void k_pbd_ventry(uint64_t n, const uint8_t *_
     for (;;) {
         if (in.p == in.end) {  // the innermost message is read: back to its parent
             if (depth == 0) break;
-            const uint64_t x = stk[--depth * 256 + threadIdx.x];
-            in.end = base + (x & 0xffffffffffull);
-            msg = (uint32_t)(x >> 40) & 0xff;
-            role = (uint32_t)(x >> 48);
+            ve_pop(stk, depth, base, in.end, msg, role);
             continue;
         }
         uint32_t f, wt;
@@ -665,8 +678,7 @@ __global__ __launch_bounds__(256) void k_pbd_ventry(uint64_t n, const uint8_t *_
                 break;
             default: break;
             }
-            stk[depth++ * 256 + threadIdx.x] =
-                (uint64_t)(in.end - base) | (uint64_t)msg << 40 | (uint64_t)role << 48;
+            ve_push(stk, depth, base, in.end, msg, role);
             in.end = in.p + len;
             role = ve_child_role(role, f);
             msg = kind - fM;
@@ -731,6 +743,197 @@ __global__ __launch_bounds__(256) void k_pbd_ventry(uint64_t n, const uint8_t *_
     v.dual_end[p] = clen ? cb + clen : (ndual == 1 ? dbeg + dlen : o0);
 }
 
+// ---------------------------------------------------------------- VerifiableTx
+// proto.Unmarshal into schema.VerifiableTx as pkg/client reads the answer of a
+// verified write (VerifiedSet client.go:1337-1391, SetAll streams.go:205-260,
+// VerifiedSetReferenceAt :1716-1770, VerifiedZAddAt :1882-1940) or of
+// VerifiedTxByID (:1554-1583): the envelope pass rooted one level below
+// k_pbd_ventry's, over the same schema table (kVeSchema) and the same LDS
+// stack (ve_push / ve_pop).
+// Beyond what that kernel reads, the roles of Tx.entries, their KVMetadata and
+// the header's TxMetadata:
+enum : uint32_t { rTxEntry = rIncl + 1, rTmd, rTexp, rHmd };
+__device__ __forceinline__ uint32_t vtx_child_role(uint32_t role, uint32_t f) {
+    switch (role * 16 + f) {
+    case rTx * 16 + 2: return rTxEntry;
+    case rTxEntry * 16 + 4: return rTmd;
+    case rTmd * 16 + 2: return rTexp;
+    case rHdr * 16 + 9: return rHmd;
+    default: return ve_child_role(role, f);
+    }
+}
+
+// One VerifiableTx per lane.  WRITE = false: validate, status (the whole
+// ladder of the call, include/immustore_merkle.h: it depends on no hash), the
+// live flag (status MH_OK and the count rule held) and the DualProof bytes to
+// concatenate; WRITE = true: the tx header with its canonical metadata, the
+// DualProof range, and for a live write answer one VtxRec per entry i < K at
+// slot spec_off[p] + i (TxFromProto, database_protoconv.go:69-95, keeps key,
+// hValue and metadata of every entry).  Entries beyond K are validated and
+// counted only.  Reads stay inside the message as in k_pbd_ventry.
+template <bool WRITE>
+__global__ __launch_bounds__(256) void k_pbd_vtx(uint64_t n, const uint8_t *__restrict__ msgs,
+                                                 const uint64_t *__restrict__ msg_off, VtxArrays v,
+                                                 int32_t *__restrict__ status) {
+    __shared__ uint64_t stk[kVeDepth * 256];
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const uint64_t o0 = msg_off[p], o1 = msg_off[p + 1] >= o0 ? msg_off[p + 1] : o0;
+    const uint32_t kind = v.kind[p];
+    const uint64_t s0 = v.spec_off[p], K = v.spec_off[p + 1] - s0;
+    const bool skip = WRITE && status[p] != MH_OK;
+    const bool rec_on = WRITE && !skip && kind != MH_VTX_TX_BY_ID && v.live[p];
+    VtxRec *recs = WRITE ? v.recs + (s0 - v.spec_base) : nullptr;
+    mh_tx_header *h = WRITE ? v.hdr + p : nullptr;
+    if (WRITE) *h = mh_tx_header{};
+    const uint8_t *base = msgs + o0;
+    PbIn in{base, skip ? base : msgs + o1};
+    uint32_t msg = vVtx, role = rVtx, depth = 0, seen = 0;
+    uint64_t nent = 0, hn = 0;
+    int32_t ver = 0;
+    MdState md;
+    // the open TxEntry: key, hValue, KVMetadata flags (eDel / eExp / eNix)
+    const uint8_t *ekb = base, *ehb = base;
+    uint64_t ekl = 0, ehl = 0, eexp = 0;
+    uint32_t ef = 0;
+    uint64_t ndual = 0, dlen = 0, dbeg = 0, cpos = 0;
+    const uint64_t c0 = WRITE ? v.cat_off[p] : 0, clen = WRITE ? v.cat_off[p + 1] - c0 : 0;
+    bool ok = true;
+    for (;;) {
+        if (in.p == in.end) {  // the innermost message is read: back to its parent
+            if (depth == 0) break;
+            if (role == rTxEntry) {  // one more element of Tx.entries
+                if (rec_on && nent < K) {
+                    VtxRec *r = recs + nent;
+                    digest_from(ehb, ehl, r->hv);
+                    r->key_pos = (uint64_t)(ekb - msgs);
+                    r->key_len = ekl;
+                    // KVMetadataFromProto + KVMetadata.Bytes() (kv_metadata.go:207-219)
+                    uint32_t k = 0;
+                    if (ef & eDel) r->md[k++] = 0;
+                    if (ef & eExp) {
+                        r->md[k++] = 1;
+                        for (int j = 7; j >= 0; j--) r->md[k++] = (uint8_t)(eexp >> (8 * j));
+                    }
+                    if (ef & eNix) r->md[k++] = 2;
+                    r->md_len = (uint8_t)k;
+                }
+                nent++;
+            }
+            ve_pop(stk, depth, base, in.end, msg, role);
+            continue;
+        }
+        uint32_t f, wt;
+        if (!(ok = in.key(f, wt))) break;
+        const uint32_t fk = f < kVeFields ? kVeSchema[msg][f] : 0;
+        if (fk == fV && wt == 0) {
+            uint64_t x;
+            if (!(ok = in.varint(x))) break;
+            const uint32_t b = x != 0;  // protowire.DecodeBool
+            switch (role * 16 + f) {
+            case rHdr * 16 + 1: if (WRITE) h->id = x; break;
+            case rHdr * 16 + 3: if (WRITE) h->ts = (int64_t)x; break;
+            case rHdr * 16 + 4: hn = (uint32_t)x; break;  // int32: the low 32 bits
+            case rHdr * 16 + 6: if (WRITE) h->bl_tx_id = x; break;
+            case rHdr * 16 + 8: ver = (int32_t)(uint32_t)x; break;
+            case rHmd * 16 + 1: md.trunc = x; break;
+            case rTmd * 16 + 1: ef = (ef & ~eDel) | (b ? eDel : 0); break;
+            case rTmd * 16 + 3: ef = (ef & ~eNix) | (b ? eNix : 0); break;
+            case rTexp * 16 + 1: eexp = x; break;
+            default: break;
+            }
+        } else if (fk == fB && wt == 2) {
+            const uint8_t *b;
+            uint64_t bl;
+            if (!(ok = in.bytes(b, bl))) break;
+            switch (role * 16 + f) {
+            case rHdr * 16 + 2: if (WRITE) digest_from(b, bl, h->prev_alh); break;
+            case rHdr * 16 + 5: if (WRITE) digest_from(b, bl, h->eh); break;
+            case rHdr * 16 + 7: if (WRITE) digest_from(b, bl, h->bl_root); break;
+            case rHmd * 16 + 2: md.extra = b, md.extra_len = bl; break;
+            case rTxEntry * 16 + 1: ekb = b, ekl = bl; break;
+            case rTxEntry * 16 + 2: ehb = b, ehl = bl; break;
+            default: break;
+            }
+        } else if (fk >= fM && wt == 2) {
+            uint64_t len;
+            if (!(ok = in.varint(len) && len <= (uint64_t)(in.end - in.p) && depth < kVeDepth))
+                break;
+            switch (role * 16 + f) {
+            case rVtx * 16 + 1: seen |= hTx; break;
+            case rTx * 16 + 1: seen |= hHdr; break;
+            case rHdr * 16 + 9: md.present = true; break;
+            case rTx * 16 + 2:
+                ekb = ehb = base;
+                ekl = ehl = eexp = 0;
+                ef = 0;
+                break;
+            case rTmd * 16 + 2: ef |= eExp; break;
+            case rDual * 16 + 1: seen |= hDs; break;
+            case rDual * 16 + 2: seen |= hDt; break;
+            case rDual * 16 + 7: seen |= hLin; break;
+            case rVtx * 16 + 2:  // one more occurrence of the DualProof
+                seen |= hDual;
+                ndual++;
+                dlen += len;
+                dbeg = (uint64_t)(in.p - msgs);
+                if (WRITE && clen) {
+                    for (uint64_t j = 0; j < len && cpos < clen; j++) v.cat[c0 + cpos++] = in.p[j];
+                }
+                break;
+            default: break;
+            }
+            ve_push(stk, depth, base, in.end, msg, role);
+            in.end = in.p + len;
+            role = vtx_child_role(role, f);
+            msg = fk - fM;
+        } else if (fk == f8 && wt == 1) {
+            if (!(ok = in.skip(8))) break;
+        } else if (!(ok = in.skip_value(f, wt))) {
+            break;
+        }
+    }
+    if (!WRITE) {
+        const bool plain = kind == MH_VTX_SET || kind == MH_VTX_SET_ALL;
+        const bool have_hdr = (seen & (hTx | hHdr)) == (hTx | hHdr);
+        const uint32_t all = hDual | hDs | hDt | hLin;
+        const uint32_t need = kind == MH_VTX_TX_BY_ID || v.state_tx[p] > 0 ? all : (hDual | hDt);
+        // Nentries is an int32 on the wire, len(kvs) an int
+        const bool cnt_ok = plain ? ((int64_t)(int32_t)(uint32_t)hn == (int64_t)K && nent == K)
+                                  : hn == 1;
+        int32_t st = MH_OK;
+        bool live = false;
+        if (!ok) st = MH_ERR_CORRUPTED_DATA;
+        else if (kind == MH_VTX_TX_BY_ID) {
+            st = (seen & need) != need ? MH_ERR_ILLEGAL_ARGUMENTS : MH_OK;
+            live = st == MH_OK;
+        } else if (!have_hdr) st = MH_ERR_ILLEGAL_ARGUMENTS;
+        else if (!cnt_ok) st = MH_OK;  // Go: ErrCorruptedData; the verdict is ok = 0
+        else if (nent == 0) st = MH_ERR_ILLEGAL_ARGUMENTS;  // tx.Entries() slices past the end
+        else if (ver != 0 && ver != 1) st = MH_ERR_UNSUPPORTED_TX_VERSION;
+        else if ((seen & need) != need) st = MH_ERR_ILLEGAL_ARGUMENTS;
+        else live = true;
+        status[p] = st;
+        v.live[p] = live;
+        v.cnt[p] = st == MH_OK && ndual > 1 ? dlen : 0;
+        return;
+    }
+    if (skip) {
+        v.dual_beg[p] = v.dual_end[p] = o0;
+        return;
+    }
+    h->nentries = (uint32_t)hn;
+    h->version = (uint32_t)ver;
+    // TxMetadataFromProto + Bytes(), in this header's own slot
+    const uint32_t ml = md_len(md);
+    h->md_off = (uint32_t)(p * kMdSlot);
+    h->md_len = ml;
+    if (ml) md_write(md, v.md_blob + p * kMdSlot);
+    const uint64_t cb = (uint64_t)(v.cat - msgs) + c0;
+    v.dual_beg[p] = clen ? cb : (ndual == 1 ? dbeg : o0);
+    v.dual_end[p] = clen ? cb + clen : (ndual == 1 ? dbeg + dlen : o0);
+}
+
 // Two device words into pinned host memory by a kernel store: a small
 // read-back without a DMA copy, which would queue behind the large
 // host-to-device chunks in flight on the copy engine.
@@ -778,6 +981,18 @@ hipError_t launch_pbd_ventry(hipStream_t st, bool write, uint64_t n, const uint8
                            status);
     else
         hipLaunchKernelGGL(k_pbd_ventry<false>, dim3(grid), dim3(256), 0, st, n, msgs, msg_off, v,
+                           status);
+    return hipGetLastError();
+}
+
+hipError_t launch_pbd_vtx(hipStream_t st, bool write, uint64_t n, const uint8_t *msgs,
+                          const uint64_t *msg_off, const VtxArrays &v, int32_t *status) {
+    if (!n) return hipSuccess;
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    if (write)
+        hipLaunchKernelGGL(k_pbd_vtx<true>, dim3(grid), dim3(256), 0, st, n, msgs, msg_off, v, status);
+    else
+        hipLaunchKernelGGL(k_pbd_vtx<false>, dim3(grid), dim3(256), 0, st, n, msgs, msg_off, v,
                            status);
     return hipGetLastError();
 }

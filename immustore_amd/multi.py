@@ -256,6 +256,24 @@ class MultiDevice:
         del keep
         return st, ok.astype(bool), ntx, nalh
 
+    def verify_verifiable_tx_pb_batch(self, msgs, kinds, specs, at_tx, state_tx, state_alh):
+        """txlayer.verify_verifiable_tx_pb_batch (whole VerifiableTx answers) over
+        the devices (parts of nearly equal message bytes) ->
+        (status[n], ok[n], new_tx[n], new_alh[n, 32], eh[n, 32])."""
+        from .txlayer import pack_verified_tx_batch
+        n = len(msgs)
+        if n == 0:
+            return (np.zeros(0, np.int32), np.zeros(0, bool), np.zeros(0, np.uint64),
+                    np.zeros((0, 32), np.uint8), np.zeros((0, 32), np.uint8))
+        b, keep = pack_verified_tx_batch(msgs, kinds, specs, at_tx, state_tx, state_alh)
+        st, ok = np.zeros(n, np.int32), np.zeros(n, np.uint8)
+        ntx, nalh = np.zeros(n, np.uint64), np.zeros((n, 32), np.uint8)
+        eh = np.zeros((n, 32), np.uint8)
+        N.check(N.load().mh_multi_verify_verifiable_tx_pb_batch(
+            self.handle, C.byref(b), _addr(st), _addr(ok), _addr(ntx), _addr(nalh), _addr(eh)))
+        del keep
+        return st, ok.astype(bool), ntx, nalh, eh
+
     def verify_document_batch(self, docs):
         """txlayer.verify_document_batch over the devices
         (mh_multi_verify_document_batch) -> (status[n], target_alh[n, 32])."""

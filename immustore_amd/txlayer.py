@@ -710,3 +710,71 @@ def decode_verifiable_entry_pb(msgs, ctx: Optional[Context] = None):
     a["incl_terms"] = a["incl_terms"][:int(a["incl_off"][n])]
     a["dual_bytes"] = a["dual_bytes"][:int(a["dual_off"][n])]
     return st[:n], a
+
+
+# ---------------------------------------------------------------- whole VerifiableTx answers
+VTX_SET, VTX_SET_ALL, VTX_REFERENCE, VTX_ZADD, VTX_TX_BY_ID = range(5)  # MH_VTX_*
+
+
+class _VerifiedTxBatch(C.Structure):
+    """mirror of mh_verified_tx_batch (include/immustore_merkle.h)"""
+    _fields_ = [("n", C.c_uint64)] + [(f, C.c_void_p) for f in (
+        "msgs", "msg_off", "kind", "spec_off", "keys", "key_off", "vals", "val_off", "at_tx",
+        "state_tx", "state_alh")]
+
+
+def pack_verified_tx_batch(msgs, kinds, specs, at_tx, state_tx, state_alh, lead: int = 0):
+    """The arrays of mh_verified_tx_batch for a list of answers -> (struct, the
+    arrays it points into: keep them alive during the call).  specs[p]: the
+    (key, value) pairs answer p owns (one for SET / REFERENCE / ZADD, the kvs of
+    SET_ALL, none for TX_BY_ID).  lead: unused bytes / specs ahead of the first
+    message, key, value and spec (every *_off[0] = lead)."""
+    n = len(msgs)
+    assert len(kinds) == n and len(specs) == n
+    flat = [kv for s in specs for kv in s]
+    T = len(flat)
+    off = np.full(n + 1, lead, np.uint64)
+    soff = np.full(n + 1, lead, np.uint64)
+    koff = np.full(lead + T + 1, lead, np.uint64)
+    voff = np.full(lead + T + 1, lead, np.uint64)
+    if n:
+        off[1:] += np.cumsum([len(x) for x in msgs], dtype=np.uint64)
+        soff[1:] += np.cumsum([len(s) for s in specs], dtype=np.uint64)
+    if T:
+        koff[lead + 1:] += np.cumsum([len(k) for k, _ in flat], dtype=np.uint64)
+        voff[lead + 1:] += np.cumsum([len(v) for _, v in flat], dtype=np.uint64)
+    buf = np.frombuffer(b"\xff" * lead + b"".join(msgs) + b"\0", np.uint8)
+    kbuf = np.frombuffer(b"\xff" * lead + b"".join(bytes(k) for k, _ in flat) + b"\0", np.uint8)
+    vbuf = np.frombuffer(b"\xff" * lead + b"".join(bytes(v) for _, v in flat) + b"\0", np.uint8)
+    kd = np.ascontiguousarray(kinds, np.uint8).reshape(-1)
+    at = np.ascontiguousarray(at_tx, np.uint64).reshape(-1)
+    stx = np.ascontiguousarray(state_tx, np.uint64).reshape(-1)
+    sa = _d32(state_alh, n)
+    assert kd.size == n and at.size == n and stx.size == n
+    keep = (buf, off, kd, soff, kbuf, koff, vbuf, voff, at, stx, sa)
+    return _VerifiedTxBatch(n, *[_addr(a) for a in keep]), keep
+
+
+def verify_verifiable_tx_pb_batch(msgs, kinds, specs, at_tx, state_tx, state_alh,
+                                  ctx: Optional[Context] = None, lead: int = 0):
+    """What pkg/client does with the VerifiableTx answer of VerifiedSet, SetAll,
+    VerifiedSetReferenceAt, VerifiedZAddAt (client.go:1337-1391, streams.go:
+    205-260, client.go:1716-1770, 1882-1940) or VerifiedTxByID (:1554-1583)
+    before the signature check, for many answers in one device pass
+    (mh_verify_verifiable_tx_pb_batch): msgs[p] the encoded VerifiableTx,
+    kinds[p] a VTX_* kind, specs[p] its (key, value) pairs, at_tx[p] the
+    reference's atTx or the requested tx, (state_tx[p], state_alh[p]) the
+    client's state (tx 0: none yet) -> (status[n] int32, ok[n] bool, new_tx[n],
+    new_alh[n, 32]: the new state where ok, eh[n, 32]: the rebuilt Eh)."""
+    n = len(msgs)
+    if n == 0:
+        return (np.zeros(0, np.int32), np.zeros(0, bool), np.zeros(0, np.uint64),
+                np.zeros((0, 32), np.uint8), np.zeros((0, 32), np.uint8))
+    b, keep = pack_verified_tx_batch(msgs, kinds, specs, at_tx, state_tx, state_alh, lead)
+    st, ok = np.zeros(n, np.int32), np.zeros(n, np.uint8)
+    ntx, nalh, eh = np.zeros(n, np.uint64), np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8)
+    N.check(N.load().mh_verify_verifiable_tx_pb_batch(_ctx(ctx).handle, C.byref(b), _addr(st),
+                                                      _addr(ok), _addr(ntx), _addr(nalh),
+                                                      _addr(eh)))
+    del keep
+    return st, ok.astype(bool), ntx, nalh, eh

@@ -986,8 +986,8 @@ int mh_verify_dual_proof_pb_batch(mh_ctx *ctx, uint64_t n, const uint8_t *msgs,
  * entry's transaction, the choice of source and target from the client's
  * state, VerifyDualProof (verification.go:127-235) and the new state.
  * FillMissingLinearAdvanceProof (a network fetch) stays with the caller, as
- * for mh_verify_dual_proof_pb_batch; VerifiedSet / VerifiedTxByID /
- * VerifiedZAdd / SQL VerifyRow are not covered.
+ * for mh_verify_dual_proof_pb_batch; SQL VerifyRow is not covered (the
+ * verified writes and VerifiedTxByID: mh_verify_verifiable_tx_pb_batch).
  *
  * Answer p is the VerifiableEntry message msgs[msg_off[p] .. msg_off[p+1])
  * for the request key keys[key_off[p] .. key_off[p+1]) (kReq.Key, without
@@ -1095,6 +1095,135 @@ typedef struct mh_verifiable_entry_decoded {
 int mh_verifiable_entry_pb_decode_batch(mh_ctx *ctx, uint64_t n, const uint8_t *msgs,
                                         const uint64_t *msg_off,
                                         mh_verifiable_entry_decoded *out, int32_t *status);
+
+/* ------------------------------------------- whole VerifiableTx answers
+ * What pkg/client does with the schema.VerifiableTx answer of a verified
+ * write or of VerifiedTxByID, up to but not including the signature check and
+ * SetState, for n answers in one device pass:
+ *   MH_VTX_SET        VerifiedSet             pkg/client/client.go:1337-1391
+ *   MH_VTX_SET_ALL    streamVerifiedSet       pkg/client/streams.go:205-260
+ *   MH_VTX_REFERENCE  VerifiedSetReferenceAt  client.go:1716-1770
+ *   MH_VTX_ZADD       VerifiedZAddAt          client.go:1882-1940
+ *   MH_VTX_TX_BY_ID   VerifiedTxByID          client.go:1554-1583 (and the
+ *                     auditor, pkg/client/auditor/auditor.go:294-312)
+ * A write is verified against the transaction rebuilt from the wire:
+ * TxFromProto (pkg/api/schema/database_protoconv.go:69-95) builds the hash
+ * tree of the TxEntry records, overwrites the header's Eh with its root, the
+ * entries the client sent are checked against that tree, the rebuilt Eh
+ * against the DualProof's target header, and the new state's Alh comes from
+ * the rebuilt header.  SQL VerifyRow is not covered.
+ *
+ * Answer p is msgs[msg_off[p] .. msg_off[p+1]) of kind[p]; it owns the specs
+ * spec_off[p] .. spec_off[p+1]) (K = their number), spec t with key
+ * keys[key_off[t] .. key_off[t+1]) and value vals[val_off[t] .. val_off[t+1]),
+ * key_off / val_off indexed by the spec's absolute number:
+ *   SET        K = 1   raw key, raw value
+ *   REFERENCE  K = 1   raw key, the referenced key; at_tx[p] = atTx
+ *   ZADD       K = 1   the finished WrapZAddReferenceAt key
+ *                      (pkg/database/meta.go:98-117), taken verbatim; no value
+ *   SET_ALL    K >= 1  raw key, raw value
+ *   TX_BY_ID   K = 0   at_tx[p] = the requested tx
+ * The prefixes of EncodeKey / EncodeEntrySpec / EncodeReference
+ * (meta.go:50-89) are added on the device.  state_tx[p] / state_alh[32 p]: the
+ * client's state, tx 0 = none yet.  All host memory, pageable or pinned; no
+ * *_off[0] need be 0.  Everything goes up once through the chunks and groups
+ * of mh_verify_dual_proof_pb_batch (MH_PB_CHUNK_MIB, MH_PB_GROUP_RATIO), chunk
+ * 0 carrying the request arrays; only status, ok, new_tx, new_alh and eh_out
+ * come back.  n == 0 returns MH_OK; a null pointer, a non-monotonic offset
+ * array, a kind outside the enum, a K that breaks the table and n above the
+ * VerifiableGet call's limit return MH_ERR_ILLEGAL_ARGUMENTS.
+ *
+ * proto.Unmarshal into schema.VerifiableTx follows the merge rules of the
+ * VerifiableGet call: fields in any order; the last scalar or bytes
+ * occurrence wins; embedded messages merge; Tx.entries occurrences append in
+ * wire order across merged tx occurrences; a dualProof that occurs more than
+ * once is the parse of the concatenation; unknown and mistyped fields and
+ * groups are skipped but must be well formed; a 10-byte varint whose last
+ * byte is above 1 is an error; the whole closure is validated, kvEntries,
+ * zEntries and signature included.
+ *
+ * status[p], first match; it depends on the structure alone, never on a hash
+ * (S = state_tx[p]):
+ *   1 MH_ERR_CORRUPTED_DATA          Unmarshal would fail
+ *   2 write kinds: MH_ERR_ILLEGAL_ARGUMENTS when tx or tx.header is absent
+ *     (the nil dereference of client.go:1337 / 1716 / 1882, streams.go:205)
+ *   3 write kinds, the count rule: SET / SET_ALL need int32(header.nentries)
+ *     == K and len(entries) == K, REFERENCE / ZADD header.nentries == 1.
+ *     Failing it is MH_OK with ok = 0 (Go: ErrCorruptedData) and nothing
+ *     below is looked at
+ *   4 REFERENCE / ZADD without any entry: MH_ERR_ILLEGAL_ARGUMENTS
+ *     (tx.Entries() slices past the end inside BuildHashTree)
+ *   5 write kinds: int(header.version) not 0 or 1 gives
+ *     MH_ERR_UNSUPPORTED_TX_VERSION (BuildHashTree's error is ignored by
+ *     TxFromProto; EntrySpecDigestFor returns this one)
+ *   6 MH_ERR_ILLEGAL_ARGUMENTS when a DualProof part Go would dereference is
+ *     missing.  Write kinds: dualProof or its targetTxHeader; with S > 0 also
+ *     sourceTxHeader or linearProof (DualProofFromProto runs only then).
+ *     TX_BY_ID: dualProof, either header or linearProof (client.go:1554 runs
+ *     it unconditionally); its tx is not looked at.  For a write kind Go
+ *     reaches this dereference only after a passing inclusion check and
+ *     returns ErrCorruptedData where that check fails; ok is 0 either way,
+ *     and the status stays independent of hashes.
+ *   7 MH_OK
+ *
+ * ok[p] of a write kind = 1 iff status[p] == MH_OK, the count rule held and
+ * all of this holds.  Entry i < K of Tx.entries gives key_i, hv_i =
+ * DigestFromProto(hValue) and md_i = KVMetadataFromProto(metadata).Bytes()
+ * (the byte rules of the VerifiableGet call; no metadata: empty).
+ *   TxEntryDigest (embedded/store/tx.go:690-731): version 1 d_i = SHA256(
+ *     BE16(len md_i) || md_i || BE16(len key_i mod 2^16) || key_i || hv_i),
+ *     version 0 d_i = SHA256(key_i || hv_i); version 0 with a non-empty md_i
+ *     gives ok = 0 (ErrMetadataUnsupported leaves the tree unbuilt, tx.Proof
+ *     fails; eh_out stays zero).
+ *   Eh' = the htree root over d_0 .. d_{K-1} (embedded/htree/htree.go:68-113);
+ *     eh_out[32 p] = Eh' whenever it is built, zeros otherwise.
+ *   Spec i: SET / SET_ALL key 0x00 || key, value 0x00 || value, metadata md_i
+ *     by position i (tx.Entries()[i].Metadata(), client.go:1353,
+ *     streams.go:224); REFERENCE key 0x00 || key, value 0x01 || BE64(at_tx)
+ *     || 0x00 || value, no metadata; ZADD the key verbatim, the empty value
+ *     (hVal = SHA256 of nothing), no metadata.  SET alone gives ok = 0 when
+ *     md_0 has the deleted attribute (client.go:1355).  x_i =
+ *     EntrySpecDigest_v0 / _v1 (embedded/store/verification.go:257-302; v0
+ *     ignores metadata); j_i = the first j < K with key_j equal to the spec's
+ *     key (Tx.IndexOf, tx.go:361-368), none: ok = 0; x_i == d_{j_i} is
+ *     required, which is what VerifyInclusion of the tree's own proof for
+ *     leaf j_i decides.
+ *   Eh' == DigestFromProto(dualProof.targetTxHeader.eH).
+ *   tgt = header.id, tgtAlh = Alh() of the tx header with Eh' in place of the
+ *     wire's eH (TxMetadata as for the headers of
+ *     mh_verify_dual_proof_pb_batch; version 0 drops it).  If S > 0:
+ *     VerifyDualProof(proof, S, tgt, state_alh, tgtAlh) as that call runs it
+ *     (a header version above 1 gives ok = 0, a missing LinearAdvanceProof is
+ *     verified as nil).
+ * ok[p] of TX_BY_ID (client.go:1554-1583), t = at_tx[p]: if S <= t (src,
+ * srcAlh, tgt, tgtAlh) = (S, state_alh, t, Target.Alh()), else (t,
+ * Source.Alh(), S, state_alh); with S > 0 the DualProof must verify, S == 0
+ * gives ok = 1.
+ * new_tx[p] / new_alh[32 p] = tgt / tgtAlh when ok[p] = 1, zeros otherwise. */
+enum { MH_VTX_SET = 0, MH_VTX_SET_ALL = 1, MH_VTX_REFERENCE = 2, MH_VTX_ZADD = 3, MH_VTX_TX_BY_ID = 4 };
+typedef struct mh_verified_tx_batch {
+    uint64_t n;
+    const uint8_t *msgs;
+    const uint64_t *msg_off;  /* n + 1: VerifiableTx messages */
+    const uint8_t *kind;      /* n: MH_VTX_* */
+    const uint64_t *spec_off; /* n + 1: answer p owns specs spec_off[p] .. spec_off[p+1] */
+    const uint8_t *keys;
+    const uint64_t *key_off;  /* T + 1, T = total specs */
+    const uint8_t *vals;
+    const uint64_t *val_off;  /* T + 1 */
+    const uint64_t *at_tx;    /* n: REFERENCE atTx; TX_BY_ID the requested tx; else ignored */
+    const uint64_t *state_tx; /* n: state.TxId, 0 = no state yet */
+    const uint8_t *state_alh; /* n x 32 */
+} mh_verified_tx_batch;
+int mh_verify_verifiable_tx_pb_batch(mh_ctx *ctx, const mh_verified_tx_batch *b, int32_t *status,
+                                     uint8_t *ok, uint64_t *new_tx, uint8_t *new_alh,
+                                     uint8_t *eh_out /* n x 32, may be NULL */);
+/* The same over the clique's devices, split by message bytes as
+ * mh_multi_verify_verifiable_entry_pb_batch (context 0 alone when K == 1 or
+ * n < K, K the devices). */
+int mh_multi_verify_verifiable_tx_pb_batch(mh_multi *m, const mh_verified_tx_batch *b,
+                                           int32_t *status, uint8_t *ok, uint64_t *new_tx,
+                                           uint8_t *new_alh, uint8_t *eh_out);
 
 int mh_htree_inclusion_proof_pb_decode_batch(mh_ctx *ctx, uint64_t n, const uint8_t *msgs,
                                              const uint64_t *msg_off, uint64_t *leaf,
