@@ -452,7 +452,7 @@ inline hipError_t ensure_chunk_events(mh_ctx *c, size_t n) {
 }
 
 // The frame of the fused wire verifies (pb_decode.hip: DualProofV2 and
-// DualProof v1 messages, with the ids and Alh values to verify them against).
+// DualProof v1 messages; capi_entry.hip, capi_vtx.hip: whole answers).
 // The call is bound by the copy of the messages (1.8 GB for 10^6 DualProofV2
 // at ~54 GB/s against ~11.5 ms of device work), so the batch is cut into
 // chunks of MH_PB_CHUNK_MIB of messages (default 128): a ChunkCopier issues
@@ -462,6 +462,8 @@ inline hipError_t ensure_chunk_events(mh_ctx *c, size_t n) {
 // open() checks the arguments, takes c->mu (held until the frame goes out of
 // scope: declare the ChunkCopier after it), cuts the batch and makes the
 // events; fill() lists the copies once the caller has laid out its buffer.
+// A call that works group by group then calls group() and, per group,
+// wait_group().
 struct PbChunkFrame {
     std::unique_lock<std::mutex> lk;
     uint64_t n = 0, m0 = 0, mb = 0;  // messages, msg_off[0], message bytes
@@ -469,19 +471,19 @@ struct PbChunkFrame {
     std::vector<uint64_t> cut{0};    // chunk k holds messages [cut[k], cut[k + 1])
     std::vector<uint64_t> longest;   // each chunk's longest message
     int nch = 0;
-    const uint8_t *msgs = nullptr, *src_alh = nullptr, *tgt_alh = nullptr;
-    const uint64_t *msg_off = nullptr, *src = nullptr, *tgt = nullptr;
+    std::vector<int> gcut{0};        // group(): the groups' first chunks
+    int ng = 0;
+    uint64_t group_n = 0, group_bytes = 0;  // messages / message bytes of the largest group
+    const uint8_t *msgs = nullptr;
+    const uint64_t *msg_off = nullptr;
 
-    // n > 0; have_outs: the caller's result pointers are all there
+    // n > 0; have_rest: the caller's other pointers are all there
     int open(mh_ctx *c, uint64_t n_, const uint8_t *msgs_, const uint64_t *msg_off_,
-             const uint64_t *src_, const uint64_t *tgt_, const uint8_t *src_alh_,
-             const uint8_t *tgt_alh_, bool have_outs) {
-        if (!msg_off_ || !src_ || !tgt_ || !src_alh_ || !tgt_alh_ || !have_outs)
-            return MH_ERR_ILLEGAL_ARGUMENTS;
-        n = n_, msgs = msgs_, msg_off = msg_off_, src = src_, tgt = tgt_;
-        src_alh = src_alh_, tgt_alh = tgt_alh_;
+             bool have_rest) {
+        if (!msg_off_ || !have_rest) return MH_ERR_ILLEGAL_ARGUMENTS;
+        n = n_, msgs = msgs_, msg_off = msg_off_;
         // a header's md_off is 32 bits over 2 n metadata slots
-        if (2 * n * (uint64_t)MH_MAX_TX_METADATA_LEN > 0xffffffffull) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (2 * n * (uint64_t)kMdSlot > 0xffffffffull) return MH_ERR_ILLEGAL_ARGUMENTS;
         if (n > 0x7fffffffull) return MH_ERR_ILLEGAL_ARGUMENTS;  // hipcub's int item count
         if (!monotonic(msg_off, n)) return MH_ERR_ILLEGAL_ARGUMENTS;
         m0 = msg_off[0], mb = msg_off[n] - m0;
@@ -518,10 +520,11 @@ struct PbChunkFrame {
     // message takes a lane, bytes >= ratio x longest (MH_PB_GROUP_RATIO,
     // default 16384; 0: every chunk alone): short messages keep the
     // chunk-by-chunk pipeline, long ones wait for more of the batch.
-    std::vector<int> groups() const {
+    // Sets gcut, ng and the largest group's sizes (what one group's scratch
+    // is made for).
+    void group() {
         uint64_t ratio = 16384;
         if (const char *e = getenv("MH_PB_GROUP_RATIO")) ratio = (uint64_t)std::max(0, atoi(e));
-        std::vector<int> gcut{0};
         for (int k = 0; k < nch;) {
             uint64_t bytes = 0, lm = 0;
             int j = k;
@@ -531,27 +534,33 @@ struct PbChunkFrame {
                 j++;
             } while (j < nch && bytes / std::max<uint64_t>(lm, 1) < ratio);
             gcut.push_back(j);
+            group_n = std::max(group_n, cut[j] - cut[k]);
+            group_bytes = std::max(group_bytes, bytes);
             k = j;
         }
-        return gcut;
+        ng = (int)gcut.size() - 1;
     }
-    // chunk 0 carries the per-message arrays whole (offsets, ids, Alh values,
-    // sources then targets at d_alh: few large copies -- each copy call costs
-    // the DMA engine ~0.1 ms of setup) and the first messages, chunk k its
-    // messages; message byte msg_off[i] lands at d_msg + msg_off[i] - m0
-    void fill(ChunkCopier &cc, uint8_t *d_msg, uint8_t *d_off, uint8_t *d_src, uint8_t *d_tgt,
-              uint8_t *d_alh) const {
+    // chunk 0 carries the caller's per-message arrays whole (chunk0: offsets,
+    // ids, Alh values, a request's keys ...: few large copies -- each copy call
+    // costs the DMA engine ~0.1 ms of setup) and the first messages, chunk k
+    // its messages; message byte msg_off[i] lands at d_msg + msg_off[i] - m0
+    void fill(ChunkCopier &cc, uint8_t *d_msg, std::vector<ChunkCopier::Piece> chunk0) const {
         cc.chunks.resize(nch);
-        cc.chunks[0] = {{d_off, msg_off, (n + 1) * 8},
-                        {d_src, src, n * 8},
-                        {d_tgt, tgt, n * 8},
-                        {d_alh, src_alh, n * 32},
-                        {d_alh + n * 32, tgt_alh, n * 32}};
+        cc.chunks[0] = std::move(chunk0);
         for (int k = 0; k < nch; k++) {
             const uint64_t lo = cut[k], hi = cut[k + 1];
             cc.chunks[k].push_back({d_msg + (msg_off[lo] - m0), msgs + msg_off[lo],
                                     msg_off[hi] - msg_off[lo]});
         }
+    }
+    // group g = messages [lo, lo + nk): the compute stream waits for its chunks
+    int wait_group(mh_ctx *c, ChunkCopier &cc, int g, uint64_t &lo, uint64_t &nk) const {
+        for (int k = gcut[g]; k < gcut[g + 1]; k++) {
+            MH_HIP(cc.wait(k));
+            MH_HIP(hipStreamWaitEvent(c->stream, c->ev_chunks[k], 0));
+        }
+        lo = cut[gcut[g]], nk = cut[gcut[g + 1]] - lo;
+        return MH_OK;
     }
 };
 
@@ -699,13 +708,43 @@ int dual_proof_v2_core(hipStream_t st, Timer *tm, uint64_t n, const mh_tx_header
 // nk, Q) device bytes, 256-byte aligned.  Only launches on st: no copy from or
 // to the host, no synchronisation.
 uint64_t dual_proof_v1_scratch_bytes(uint64_t nk, uint64_t Q);
+int dual_proof_v1_core(hipStream_t st, Timer *tm, uint64_t nk, const Dual1Arrays &o,
+                       const uint64_t *src, const uint64_t *tgt, const uint8_t *src_alh,
+                       const uint8_t *tgt_alh, const int32_t *status, uint64_t md_blob_len,
+                       Dp1V0Metadata v0_md, uint64_t Q, uint8_t *scratch, uint8_t *ok);
+// The decode of a batch of DualProof (v1) messages on the device
+// (pb_decode.hip, k_pbd_dual1): THE statement of that stage, behind
+// mh_dual_proof_pb_decode_batch and the three fused verifies.  Two steps on
+// c->stream with the caller between them: it knows the totals before any term
+// is written, and makes the term area.
+// The stage's regions for up to M proofs at a time, in the caller's Layout.
+struct Dual1Scratch {
+    uint64_t cnt, so, scan, hdr, md, tbl_alh, flags, lin;
+    size_t scan_bytes;  // temp of one scan over M items, at scan (the caller's scans may use it)
+    // scanned offset array j of a step over nk <= M proofs: nk + 1 entries
+    uint64_t *off(uint8_t *base, int j, uint64_t nk) const {
+        return (uint64_t *)(base + so) + (uint64_t)j * (nk + 1);
+    }
+};
+Dual1Scratch dual1_decode_scratch(Layout &L, uint64_t M);
+// Size step: message p is dmsg[beg[p] .. end[p]), or .. beg[p + 1]) with a
+// null end.  Status, the counts and their scanned offsets (device); totals[j]
+// = offset array j's last entry, on the host: the stream is synchronised.
+int dual1_decode_size(mh_ctx *c, uint64_t nk, const uint8_t *dmsg, const uint64_t *beg,
+                      const uint64_t *end, uint8_t *base, const Dual1Scratch &s, int32_t *status,
+                      uint64_t totals[kCounts]);
+// The term area those totals need, in the caller's Layout: the five lists,
+// the nested terms, totals[kQ] + 1 nested offsets.
+struct Dual1Terms {
+    uint64_t terms[5], qterms, qoff;
+};
+Dual1Terms dual1_decode_terms(Layout &T, const uint64_t totals[kCounts]);
+// Write step: everything of o, the terms at dt + t (device); same messages
+// and status as the size step.
+int dual1_decode_write(mh_ctx *c, uint64_t nk, const uint8_t *dmsg, const uint64_t *beg,
+                       const uint64_t *end, uint8_t *base, const Dual1Scratch &s, uint8_t *dt,
+                       const Dual1Terms &t, int32_t *status, Dual1Arrays &o);
 // The decoders' kernels other translation units launch (pb_decode.hip).
-// DualProof (v1) messages in begin-and-end form: message p is msgs[beg[p] ..
-// end[p]); write = false: status and the kCounts x n counts, write = true: o
-// at its scanned offsets (k_pbd_dual1).
-hipError_t launch_pbd_dual1_range(hipStream_t st, bool write, uint64_t n, const uint8_t *msgs,
-                                  const uint64_t *beg, const uint64_t *end, uint64_t *cnt,
-                                  const Dual1Arrays &o, int32_t *status);
 // VerifiableEntry envelopes (k_pbd_ventry): message p is msgs[msg_off[p] ..
 // msg_off[p + 1]); write = false: status and v.cnt, write = true: the rest of v
 hipError_t launch_pbd_ventry(hipStream_t st, bool write, uint64_t n, const uint8_t *msgs,
@@ -716,11 +755,6 @@ hipError_t launch_pbd_vtx(hipStream_t st, bool write, uint64_t n, const uint8_t 
                           const uint64_t *msg_off, const VtxArrays &v, int32_t *status);
 // small read-backs by kernel stores into pinned host memory (out: device view)
 hipError_t launch_put2_host(hipStream_t st, const uint64_t *a, const uint64_t *b, uint64_t *out);
-hipError_t launch_put7_host(hipStream_t st, const uint64_t *so, uint64_t n, uint64_t *out);
-int dual_proof_v1_core(hipStream_t st, Timer *tm, uint64_t nk, const Dual1Arrays &o,
-                       const uint64_t *src, const uint64_t *tgt, const uint8_t *src_alh,
-                       const uint8_t *tgt_alh, const int32_t *status, uint64_t md_blob_len,
-                       Dp1V0Metadata v0_md, uint64_t Q, uint8_t *scratch, uint8_t *ok);
 int build_many_dev(mh_ctx *c, hipStream_t st, uint64_t ntrees, const uint64_t *leaf_off,
                    const uint8_t *d_dig, uint8_t *d_roots, DevBuf &s_lv, DevBuf &s_lo);
 int run_tree_plan(mh_ctx *c, hipStream_t st, const TreePlan &P, uint64_t ntrees, uint64_t nleaves,

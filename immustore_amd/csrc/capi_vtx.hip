@@ -11,24 +11,18 @@
 //   EncodeEntrySpec / EncodeReference, EntrySpecDigest,
 //   Tx.IndexOf, the inclusion decision                  k_vtx_spec
 //   BuildHashTree  tx.go:332-355                        build_many_dev (capi_tx.hip)
-//   DualProofFromProto  database_protoconv.go:213-287   k_pbd_dual1 (pb_decode.hip)
+//   DualProofFromProto  database_protoconv.go:213-287   dual1_decode_size / _write
+//                                                       (k_pbd_dual1, pb_decode.hip)
 //   deleted / Eh rules, TxHeader.Alh, source and target k_vtx_answer
 //   store.VerifyDualProof  verification.go:127-235      dual_proof_v1_core (capi_tx.hip)
 //
 // The frame is the one of mh_verify_verifiable_entry_pb_batch: the messages
 // go up in chunks (PbChunkFrame, ChunkCopier), chunk 0 carrying the
-// per-answer arrays and the request's keys and values; groups of chunks are
-// decoded and verified as they land.  The host knows every tree's shape from
-// the request (spec_off), so the entry records need no scan.
-#include <hipcub/hipcub.hpp>
-
+// per-answer arrays and the request's keys and values; groups of chunks
+// (PbChunkFrame::group / wait_group) are decoded and verified as they land.
+// The host knows every tree's shape from the request (spec_off), so the entry
+// records need no scan.
 #include "capi_internal.hpp"
-
-namespace {
-
-constexpr uint32_t kMdSlot = MH_MAX_TX_METADATA_LEN;  // metadata bytes per header
-
-}  // namespace
 
 extern "C" int mh_verify_verifiable_tx_pb_batch(mh_ctx *c, const mh_verified_tx_batch *b,
                                                 int32_t *status, uint8_t *ok, uint64_t *new_tx,
@@ -68,34 +62,19 @@ extern "C" int mh_verify_verifiable_tx_pb_batch(mh_ctx *c, const mh_verified_tx_
         const uint64_t v0 = val_off[s0], vb = val_off[s0 + T] - v0;
         if ((kb && !b->keys) || (vb && !b->vals)) return MH_ERR_ILLEGAL_ARGUMENTS;
         PbChunkFrame F;
-        // at_tx / state_tx / state_alh stand where the dual-proof calls pass
-        // src / tgt / the Alh values: the frame only checks and keeps them
-        if (int e = F.open(c, n, b->msgs, b->msg_off, b->at_tx, b->state_tx, b->state_alh,
-                           b->state_alh, status && ok && new_tx && new_alh))
-            return e;
-        const uint64_t *msg_off = b->msg_off;
-        const std::vector<uint64_t> &cut = F.cut;
-        const uint64_t m0 = F.m0, mb = F.mb;
-        const int nch = F.nch;
+        if (int e = F.open(c, n, b->msgs, b->msg_off, status && ok && new_tx && new_alh)) return e;
         hipStream_t st = c->stream;
         Timer *tm = c->tm();
-        const std::vector<int> gcut = F.groups();
-        const int ng = (int)gcut.size() - 1;
-        uint64_t M = 0, GB = 0, TG = 0;  // answers / message bytes / slots of the largest group
-        for (int g = 0; g < ng; g++) {
-            const uint64_t lo = cut[gcut[g]], hi = cut[gcut[g + 1]];
-            M = std::max(M, hi - lo);
-            GB = std::max(GB, msg_off[hi] - msg_off[lo]);
-            TG = std::max(TG, spec_off[hi] - spec_off[lo]);
-        }
-        size_t scan_bytes = 0;
-        MH_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const uint64_t *)nullptr,
-                                                (uint64_t *)nullptr, (int)M, st));
+        F.group();
+        const uint64_t M = F.group_n, GB = F.group_bytes;  // the largest group
+        uint64_t TG = 0;                                   // the most slots of a group
+        for (int g = 0; g < F.ng; g++)
+            TG = std::max(TG, spec_off[F.cut[F.gcut[g + 1]]] - spec_off[F.cut[F.gcut[g]]]);
         Layout L;
         // the messages and, in the same allocation (DualProof ranges are
         // relative to the messages), one group's concatenation area; the
         // caller's arrays and the results, whole; then one group's work
-        const uint64_t b_msg = L.add(mb + 16), b_cat = L.add(GB + 16), b_off = L.add((n + 1) * 8),
+        const uint64_t b_msg = L.add(F.mb + 16), b_cat = L.add(GB + 16), b_off = L.add((n + 1) * 8),
                        b_kind = L.add(n), b_soff = L.add((n + 1) * 8), b_at = L.add(n * 8),
                        b_stx = L.add(n * 8), b_salh = L.add(n * 32), b_koff = L.add((T + 1) * 8),
                        b_keys = L.add(kb + 16), b_voff = L.add((T + 1) * 8), b_vals = L.add(vb + 16),
@@ -109,42 +88,30 @@ extern "C" int mh_verify_verifiable_tx_pb_batch(mh_ctx *c, const mh_verified_tx_
                        b_dend = L.add(M * 8), b_dst2 = L.add(M * 4), b_vsrc = L.add(M * 8),
                        b_vtgt = L.add(M * 8), b_valh = L.add(2 * M * 32), b_pok = L.add(M),
                        b_dok2 = L.add(M);
-        const uint64_t b_cnt = L.add(kCounts * M * 8), b_so = L.add(kCounts * (M + 1) * 8),
-                       b_scan = L.add(scan_bytes), b_h = L.add(2 * M * sizeof(mh_tx_header)),
-                       b_md = L.add(2 * M * (uint64_t)kMdSlot), b_tba = L.add(M * 32),
-                       b_flags = L.add(2 * M), b_lsrc = L.add(2 * M * 8);
+        const Dual1Scratch ds = dual1_decode_scratch(L, M);
         MH_HIP(c->s_tx.ensure(L.total));
         uint8_t *base = c->s_tx.as<uint8_t>();
         auto U = [&](uint64_t off) { return (uint64_t *)(base + off); };
         ChunkCopier cc(c);
-        cc.chunks.resize(nch);
-        cc.chunks[0] = {{base + b_off, msg_off, (n + 1) * 8},
-                        {base + b_kind, b->kind, n},
-                        {base + b_soff, spec_off, (n + 1) * 8},
-                        {base + b_at, b->at_tx, n * 8},
-                        {base + b_stx, b->state_tx, n * 8},
-                        {base + b_salh, b->state_alh, n * 32},
-                        {base + b_koff, key_off + s0, (T + 1) * 8},
-                        {base + b_keys, b->keys ? b->keys + k0 : nullptr, kb},
-                        {base + b_voff, val_off + s0, (T + 1) * 8},
-                        {base + b_vals, b->vals ? b->vals + v0 : nullptr, vb}};
-        for (int k = 0; k < nch; k++) {
-            const uint64_t lo = cut[k], hi = cut[k + 1];
-            cc.chunks[k].push_back({base + b_msg + (msg_off[lo] - m0), b->msgs + msg_off[lo],
-                                    msg_off[hi] - msg_off[lo]});
-        }
+        F.fill(cc, base + b_msg,
+               {{base + b_off, b->msg_off, (n + 1) * 8},
+                {base + b_kind, b->kind, n},
+                {base + b_soff, spec_off, (n + 1) * 8},
+                {base + b_at, b->at_tx, n * 8},
+                {base + b_stx, b->state_tx, n * 8},
+                {base + b_salh, b->state_alh, n * 32},
+                {base + b_koff, key_off + s0, (T + 1) * 8},
+                {base + b_keys, b->keys ? b->keys + k0 : nullptr, kb},
+                {base + b_voff, val_off + s0, (T + 1) * 8},
+                {base + b_vals, b->vals ? b->vals + v0 : nullptr, vb}});
         MH_HIP(cc.start());
-        const uint8_t *dmsg = base + b_msg - m0;
+        const uint8_t *dmsg = base + b_msg - F.m0;
         int32_t *dst_all = (int32_t *)(base + b_st), *dst2 = (int32_t *)(base + b_dst2);
-        uint64_t *cnt = U(b_cnt), *so = U(b_so);
         DevBuf &tb = c->s_tree;
         std::vector<uint64_t> leaf_off;
-        for (int g = 0; g < ng; g++) {
-            for (int k = gcut[g]; k < gcut[g + 1]; k++) {
-                MH_HIP(cc.wait(k));
-                MH_HIP(hipStreamWaitEvent(st, c->ev_chunks[k], 0));
-            }
-            const uint64_t lo = cut[gcut[g]], nk = cut[gcut[g + 1]] - lo;
+        for (int g = 0; g < F.ng; g++) {
+            uint64_t lo, nk;
+            if (int e = F.wait_group(c, cc, g, lo, nk)) return e;
             const uint64_t Tg = spec_off[lo + nk] - spec_off[lo];
             const uint64_t *doff = (const uint64_t *)(base + b_off) + lo;
             int32_t *dst = dst_all + lo;
@@ -168,12 +135,7 @@ extern "C" int mh_verify_verifiable_tx_pb_batch(mh_ctx *c, const mh_verified_tx_
                 MH_HIP(launch_pbd_vtx(st, false, nk, dmsg, doff, v, dst));
             }
             uint64_t *vso = U(b_vso);
-            MH_HIP(hipMemsetAsync(vso, 0, 8, st));
-            {
-                size_t sb = scan_bytes;
-                MH_HIP(hipcub::DeviceScan::InclusiveSum(base + b_scan, sb, (const uint64_t *)v.cnt,
-                                                        vso + 1, (int)nk, st));
-            }
+            MH_HIP(scan_offsets_u64(st, nk, v.cnt, vso, base + ds.scan, ds.scan_bytes));
             volatile uint64_t *tot = c->p_small.as<volatile uint64_t>();
             MH_HIP(launch_put2_host(st, vso + nk, vso + nk, (uint64_t *)c->p_small.p));
             MH_HIP(hipStreamSynchronize(st));
@@ -220,52 +182,22 @@ extern "C" int mh_verify_verifiable_tx_pb_batch(mh_ctx *c, const mh_verified_tx_
             if (int e = build_many_dev(c, st, nk, leaf_off.data(), w.dig, base + b_roots,
                                        c->s_digests, c->s_offs))
                 return e;
-            // 3. DualProofFromProto over the located ranges: sizes, the eight
-            // scans, the seven totals, the write pass
-            {
-                TimerScope ts(tm, "pbd_dual1_size", st);
-                MH_HIP(launch_pbd_dual1_range(st, false, nk, dmsg, v.dual_beg, v.dual_end, cnt,
-                                              Dual1Arrays{}, dst2));
-            }
-            for (int j = 0; j < kCounts; j++) {
-                uint64_t *sj = so + (uint64_t)j * (nk + 1);
-                MH_HIP(hipMemsetAsync(sj, 0, 8, st));
-                size_t sb = scan_bytes;
-                MH_HIP(hipcub::DeviceScan::InclusiveSum(base + b_scan, sb,
-                                                        (const uint64_t *)(cnt + j * nk), sj + 1,
-                                                        (int)nk, st));
-            }
-            MH_HIP(launch_put7_host(st, so, nk, (uint64_t *)c->p_small.p));
-            MH_HIP(hipStreamSynchronize(st));
-            uint64_t totals[kMd];
-            for (int j = 0; j < kMd; j++) totals[j] = tot[j];
+            // 3. DualProofFromProto over the located ranges; its term area, the
+            // Alh messages and the verifier's scratch in one allocation
+            uint64_t totals[kCounts];
+            if (int e = dual1_decode_size(c, nk, dmsg, v.dual_beg, v.dual_end, base, ds, dst2, totals))
+                return e;
             const uint64_t Q = totals[kQ];
             Layout TL;
-            uint64_t t_terms[5];
-            for (int j = 0; j < 5; j++) t_terms[j] = TL.add(totals[j] * 32);
-            const uint64_t t_qt = TL.add(totals[kQT] * 32), t_qo = TL.add((Q + 1) * 8),
-                           t_alh = TL.add(nk * kTxInnerStride),
+            const Dual1Terms dterms = dual1_decode_terms(TL, totals);
+            const uint64_t t_alh = TL.add(nk * kTxInnerStride),
                            t_core = TL.add(dual_proof_v1_scratch_bytes(nk, Q));
             MH_HIP(tb.ensure(TL.total + 8));
             uint8_t *dt = tb.as<uint8_t>();
             Dual1Arrays o;
-            for (int j = 0; j < kCounts; j++) o.off[j] = so + (uint64_t)j * (nk + 1);
-            for (int j = 0; j < 5; j++) o.terms[j] = dt + t_terms[j];
-            o.qterms = dt + t_qt;
-            o.qoff = (uint64_t *)(dt + t_qo);
-            o.src_hdr = (mh_tx_header *)(base + b_h);
-            o.tgt_hdr = o.src_hdr + nk;
-            o.md_blob = base + b_md;
-            o.tbl_alh = base + b_tba;
-            o.has_lin = base + b_flags;
-            o.has_adv = base + b_flags + nk;
-            o.lin_src = U(b_lsrc);
-            o.lin_tgt = o.lin_src + nk;
-            {
-                TimerScope ts(tm, "pbd_dual1_write", st);
-                MH_HIP(launch_pbd_dual1_range(st, true, nk, dmsg, v.dual_beg, v.dual_end, nullptr, o,
-                                              dst2));
-            }
+            if (int e = dual1_decode_write(c, nk, dmsg, v.dual_beg, v.dual_end, base, ds, dt, dterms,
+                                           dst2, o))
+                return e;
             // 4. the answer: its slots, the Eh rules, the Alh; source and
             // target; VerifyDualProof (verification.go:127-235); the verdict
             w.src_hdr = o.src_hdr;

@@ -242,6 +242,8 @@ hipError_t launch_advance_chain_gated(hipStream_t st, Timer *tm, uint64_t n, con
 // them: the five term lists, the nested InclusionProofs of the advance proof
 // and their terms, the canonical metadata bytes.
 enum : int { kI = 0, kC, kL, kLin, kAdv, kQ, kQT, kMd, kCounts };
+// A decoder's metadata blob: header p's canonical bytes start at p * kMdSlot.
+constexpr uint32_t kMdSlot = MH_MAX_TX_METADATA_LEN;
 
 // A batch of decoded DualProofs on the device, in the layout of
 // mh_dual_proof_batch: what the decoder's write pass (pb_decode.hip) fills and
@@ -600,6 +602,9 @@ uint64_t pb_scratch_bytes(uint64_t n);
 size_t pb_scan_temp_bytes(uint64_t n);
 hipError_t scan_offsets_u64(hipStream_t st, uint64_t n, const uint64_t *in, uint64_t *out,
                             uint8_t *temp);
+// the same with temp made for more items than n: temp_bytes is the size it was made with
+hipError_t scan_offsets_u64(hipStream_t st, uint64_t n, const uint64_t *in, uint64_t *out,
+                            uint8_t *temp, size_t temp_bytes);
 hipError_t launch_pb_dual_v2(hipStream_t st, Timer *tm, int phase, const uint8_t *dlog,
                              uint64_t size, uint64_t n, const MhTxHeader *src,
                              const MhTxHeader *tgt, const uint8_t *md_blob, uint8_t *out,

@@ -25,16 +25,13 @@
 //
 // One lane per message, two passes: the first validates and counts the
 // inclusion / consistency terms and the canonical metadata bytes, the offsets
-// are scanned (hipcub), the second writes the headers, the terms and the
-// metadata (packed: only the bytes that exist travel back to the host).
-#include <hipcub/hipcub.hpp>
-
+// are scanned (scan_offsets_u64), the second writes the headers, the terms and
+// the metadata (packed: only the bytes that exist travel back to the host).
 #include "capi_internal.hpp"
 
 namespace {
 
-constexpr uint32_t kMdSlot = MH_MAX_TX_METADATA_LEN;  // metadata bytes per header
-constexpr uint32_t kMaxExtra = 256;                    // maxExtraLen, tx_metadata.go
+constexpr uint32_t kMaxExtra = 256;                   // maxExtraLen, tx_metadata.go
 
 struct PbIn {
     const uint8_t *p, *end;
@@ -946,11 +943,11 @@ __global__ void k_put2_host(const uint64_t *__restrict__ a, const uint64_t *__re
     }
 }
 
-// The seven term / proof totals of a chunk (entry n of each scanned offset
-// array, kI .. kQT) into pinned host memory, as k_put2_host does for two.
-// so holds the kCounts offset arrays back to back, n + 1 entries each.
-__global__ void k_put7_host(const uint64_t *__restrict__ so, uint64_t n, volatile uint64_t *out) {
-    if (threadIdx.x < kMd) {
+// The eight totals of a group (entry n of each scanned offset array, kI ..
+// kMd) into pinned host memory, as k_put2_host does for two.  so holds the
+// kCounts offset arrays back to back, n + 1 entries each.
+__global__ void k_put8_host(const uint64_t *__restrict__ so, uint64_t n, volatile uint64_t *out) {
+    if (threadIdx.x < kCounts) {
         out[threadIdx.x] = so[(uint64_t)threadIdx.x * (n + 1) + n];
         __threadfence_system();
     }
@@ -958,9 +955,11 @@ __global__ void k_put7_host(const uint64_t *__restrict__ so, uint64_t n, volatil
 
 }  // namespace
 
-hipError_t launch_pbd_dual1_range(hipStream_t st, bool write, uint64_t n, const uint8_t *msgs,
-                                  const uint64_t *beg, const uint64_t *end, uint64_t *cnt,
-                                  const Dual1Arrays &o, int32_t *status) {
+// write = false: status and the kCounts x n counts, write = true: o at its
+// scanned offsets
+static hipError_t launch_pbd_dual1(hipStream_t st, bool write, uint64_t n, const uint8_t *msgs,
+                                   const uint64_t *beg, const uint64_t *end, uint64_t *cnt,
+                                   const Dual1Arrays &o, int32_t *status) {
     if (!n) return hipSuccess;
     const unsigned grid = (unsigned)((n + 255) / 256);
     if (write)
@@ -970,6 +969,72 @@ hipError_t launch_pbd_dual1_range(hipStream_t st, bool write, uint64_t n, const 
         hipLaunchKernelGGL(k_pbd_dual1<false>, dim3(grid), dim3(256), 0, st, n, msgs, beg, end, cnt,
                            Dual1Arrays{}, status);
     return hipGetLastError();
+}
+
+Dual1Scratch dual1_decode_scratch(Layout &L, uint64_t M) {
+    Dual1Scratch s;
+    s.cnt = L.add(kCounts * M * 8);
+    s.so = L.add(kCounts * (M + 1) * 8);
+    s.scan_bytes = pb_scan_temp_bytes(M);
+    s.scan = L.add(s.scan_bytes);
+    s.hdr = L.add(2 * M * sizeof(mh_tx_header));
+    s.md = L.add(2 * M * (uint64_t)kMdSlot);
+    s.tbl_alh = L.add(M * 32);
+    s.flags = L.add(2 * M);
+    s.lin = L.add(2 * M * 8);
+    return s;
+}
+
+int dual1_decode_size(mh_ctx *c, uint64_t nk, const uint8_t *dmsg, const uint64_t *beg,
+                      const uint64_t *end, uint8_t *base, const Dual1Scratch &s, int32_t *status,
+                      uint64_t totals[kCounts]) {
+    hipStream_t st = c->stream;
+    MH_HIP(c->p_small.ensure(kCounts * 8));
+    uint64_t *cnt = (uint64_t *)(base + s.cnt);
+    {
+        TimerScope ts(c->tm(), "pbd_dual1_size", st);
+        MH_HIP(launch_pbd_dual1(st, false, nk, dmsg, beg, end, cnt, Dual1Arrays{}, status));
+    }
+    for (int j = 0; j < kCounts; j++)
+        MH_HIP(scan_offsets_u64(st, nk, cnt + j * nk, s.off(base, j, nk), base + s.scan,
+                                s.scan_bytes));
+    // the totals size the term area: stored by a kernel into pinned memory
+    // (the DMA engine is busy with the next chunks)
+    volatile uint64_t *tot = c->p_small.as<volatile uint64_t>();
+    hipLaunchKernelGGL(k_put8_host, dim3(1), dim3(64), 0, st, s.off(base, 0, nk), nk,
+                       (uint64_t *)c->p_small.p);
+    MH_HIP(hipGetLastError());
+    MH_HIP(hipStreamSynchronize(st));
+    for (int j = 0; j < kCounts; j++) totals[j] = tot[j];
+    return MH_OK;
+}
+
+Dual1Terms dual1_decode_terms(Layout &T, const uint64_t totals[kCounts]) {
+    Dual1Terms t;
+    for (int j = 0; j < 5; j++) t.terms[j] = T.add(totals[j] * 32);
+    t.qterms = T.add(totals[kQT] * 32);
+    t.qoff = T.add((totals[kQ] + 1) * 8);
+    return t;
+}
+
+int dual1_decode_write(mh_ctx *c, uint64_t nk, const uint8_t *dmsg, const uint64_t *beg,
+                       const uint64_t *end, uint8_t *base, const Dual1Scratch &s, uint8_t *dt,
+                       const Dual1Terms &t, int32_t *status, Dual1Arrays &o) {
+    for (int j = 0; j < kCounts; j++) o.off[j] = s.off(base, j, nk);
+    for (int j = 0; j < 5; j++) o.terms[j] = dt + t.terms[j];
+    o.qterms = dt + t.qterms;
+    o.qoff = (uint64_t *)(dt + t.qoff);
+    o.src_hdr = (mh_tx_header *)(base + s.hdr);
+    o.tgt_hdr = o.src_hdr + nk;
+    o.md_blob = base + s.md;
+    o.tbl_alh = base + s.tbl_alh;
+    o.has_lin = base + s.flags;
+    o.has_adv = base + s.flags + nk;
+    o.lin_src = (uint64_t *)(base + s.lin);
+    o.lin_tgt = o.lin_src + nk;
+    TimerScope ts(c->tm(), "pbd_dual1_write", c->stream);
+    MH_HIP(launch_pbd_dual1(c->stream, true, nk, dmsg, beg, end, nullptr, o, status));
+    return MH_OK;
 }
 
 hipError_t launch_pbd_ventry(hipStream_t st, bool write, uint64_t n, const uint8_t *msgs,
@@ -1002,11 +1067,6 @@ hipError_t launch_put2_host(hipStream_t st, const uint64_t *a, const uint64_t *b
     return hipGetLastError();
 }
 
-hipError_t launch_put7_host(hipStream_t st, const uint64_t *so, uint64_t n, uint64_t *out) {
-    hipLaunchKernelGGL(k_put7_host, dim3(1), dim3(64), 0, st, so, n, out);
-    return hipGetLastError();
-}
-
 extern "C" int mh_dual_proof_v2_pb_decode_batch(
     mh_ctx *c, uint64_t n, const uint8_t *msgs, const uint64_t *msg_off, mh_tx_header *src_hdr,
     mh_tx_header *tgt_hdr, uint8_t *md_blob, uint64_t *incl_off, uint8_t *incl_terms,
@@ -1029,14 +1089,12 @@ extern "C" int mh_dual_proof_v2_pb_decode_batch(
         std::lock_guard<std::mutex> lk(c->mu);
         MH_HIP(hipSetDevice(c->device));
         hipStream_t st = c->stream;
-        size_t scan_bytes = 0;
-        MH_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const uint64_t *)nullptr,
-                                                (uint64_t *)nullptr, (int)n, st));
         Layout L;
         const uint64_t b_msg = L.add(mb + 16), b_off = L.add((n + 1) * 8), b_ni = L.add(n * 8),
                        b_nc = L.add(n * 8), b_nm = L.add(n * 8), b_io = L.add((n + 1) * 8),
                        b_co = L.add((n + 1) * 8), b_mo = L.add((n + 1) * 8), b_st = L.add(n * 4),
-                       b_scan = L.add(scan_bytes), b_h = L.add(2 * n * sizeof(mh_tx_header)),
+                       b_scan = L.add(pb_scan_temp_bytes(n)),
+                       b_h = L.add(2 * n * sizeof(mh_tx_header)),
                        b_md = L.add(2 * n * (uint64_t)kMdSlot);
         MH_HIP(c->s_tx.ensure(L.total));
         uint8_t *base = c->s_tx.as<uint8_t>();
@@ -1054,13 +1112,8 @@ extern "C" int mh_dual_proof_v2_pb_decode_batch(
         MH_HIP(hipGetLastError());
         const uint64_t cnt[3] = {b_ni, b_nc, b_nm};
         uint64_t *outs[3] = {io, co, mo};
-        for (int k = 0; k < 3; k++) {
-            MH_HIP(hipMemsetAsync(outs[k], 0, 8, st));
-            size_t sb = scan_bytes;
-            MH_HIP(hipcub::DeviceScan::InclusiveSum(base + b_scan, sb,
-                                                    (const uint64_t *)(base + cnt[k]), outs[k] + 1,
-                                                    (int)n, st));
-        }
+        for (int k = 0; k < 3; k++)
+            MH_HIP(scan_offsets_u64(st, n, (const uint64_t *)(base + cnt[k]), outs[k], base + b_scan));
         uint64_t md_total = 0;
         MH_HIP(hipMemcpyAsync(incl_off, io, (n + 1) * 8, hipMemcpyDeviceToHost, st));
         MH_HIP(hipMemcpyAsync(cons_off, co, (n + 1) * 8, hipMemcpyDeviceToHost, st));
@@ -1108,12 +1161,10 @@ extern "C" int mh_htree_inclusion_proof_pb_decode_batch(mh_ctx *c, uint64_t n, c
         std::lock_guard<std::mutex> lk(c->mu);
         MH_HIP(hipSetDevice(c->device));
         hipStream_t st = c->stream;
-        size_t scan_bytes = 0;
-        MH_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const uint64_t *)nullptr,
-                                                (uint64_t *)nullptr, (int)n, st));
         Layout L;
         const uint64_t b_msg = L.add(mb + 16), b_off = L.add((n + 1) * 8), b_cnt = L.add(n * 8),
-                       b_to = L.add((n + 1) * 8), b_st = L.add(n * 4), b_scan = L.add(scan_bytes),
+                       b_to = L.add((n + 1) * 8), b_st = L.add(n * 4),
+                       b_scan = L.add(pb_scan_temp_bytes(n)),
                        b_lw = L.add(2 * n * 8);
         MH_HIP(c->s_tx.ensure(L.total));
         uint8_t *base = c->s_tx.as<uint8_t>();
@@ -1126,10 +1177,7 @@ extern "C" int mh_htree_inclusion_proof_pb_decode_batch(mh_ctx *c, uint64_t n, c
                            (const uint64_t *)(base + b_off), (uint64_t *)(base + b_cnt), nullptr,
                            nullptr, nullptr, nullptr, (int32_t *)(base + b_st));
         MH_HIP(hipGetLastError());
-        MH_HIP(hipMemsetAsync(to, 0, 8, st));
-        size_t sb = scan_bytes;
-        MH_HIP(hipcub::DeviceScan::InclusiveSum(base + b_scan, sb, (const uint64_t *)(base + b_cnt),
-                                                to + 1, (int)n, st));
+        MH_HIP(scan_offsets_u64(st, n, (const uint64_t *)(base + b_cnt), to, base + b_scan));
         MH_HIP(hipMemcpyAsync(term_off, to, (n + 1) * 8, hipMemcpyDeviceToHost, st));
         MH_HIP(hipMemcpyAsync(status, base + b_st, n * 4, hipMemcpyDeviceToHost, st));
         MH_HIP(hipStreamSynchronize(st));
@@ -1178,103 +1226,65 @@ extern "C" int mh_dual_proof_pb_decode_batch(mh_ctx *c, uint64_t n, const uint8_
         std::lock_guard<std::mutex> lk(c->mu);
         MH_HIP(hipSetDevice(c->device));
         hipStream_t st = c->stream;
-        size_t scan_bytes = 0;
-        MH_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const uint64_t *)nullptr,
-                                                (uint64_t *)nullptr, (int)n, st));
         Layout L;
-        const uint64_t b_msg = L.add(mb + 16), b_off = L.add((n + 1) * 8),
-                       b_cnt = L.add(kCounts * n * 8), b_so = L.add(kCounts * (n + 1) * 8),
-                       b_st = L.add(n * 4), b_scan = L.add(scan_bytes),
-                       b_h = L.add(2 * n * sizeof(mh_tx_header)), b_md = L.add(2 * n * (uint64_t)kMdSlot),
-                       b_tba = L.add(n * 32), b_flags = L.add(2 * n), b_ls = L.add(2 * n * 8);
+        const uint64_t b_msg = L.add(mb + 16), b_off = L.add((n + 1) * 8), b_st = L.add(n * 4);
+        const Dual1Scratch ds = dual1_decode_scratch(L, n);
         MH_HIP(c->s_tx.ensure(L.total));
         uint8_t *base = c->s_tx.as<uint8_t>();
         if (mb) MH_HIP(hipMemcpyAsync(base + b_msg, msgs + m0, mb, hipMemcpyHostToDevice, st));
         MH_HIP(hipMemcpyAsync(base + b_off, msg_off, (n + 1) * 8, hipMemcpyHostToDevice, st));
-        const unsigned grid = (unsigned)((n + 255) / 256);
         const uint8_t *dmsg = base + b_msg - m0;
-        uint64_t *cnt = (uint64_t *)(base + b_cnt), *so = (uint64_t *)(base + b_so);
-        hipLaunchKernelGGL(k_pbd_dual1<false>, dim3(grid), dim3(256), 0, st, n, dmsg,
-                           (const uint64_t *)(base + b_off), nullptr, cnt, Dual1Arrays{},
-                           (int32_t *)(base + b_st));
-        MH_HIP(hipGetLastError());
-        for (int j = 0; j < kCounts; j++) {
-            uint64_t *sj = so + (uint64_t)j * (n + 1);
-            MH_HIP(hipMemsetAsync(sj, 0, 8, st));
-            size_t sb = scan_bytes;
-            MH_HIP(hipcub::DeviceScan::InclusiveSum(base + b_scan, sb, (const uint64_t *)(cnt + j * n),
-                                                    sj + 1, (int)n, st));
-        }
+        const uint64_t *doff = (const uint64_t *)(base + b_off);
+        int32_t *dst = (int32_t *)(base + b_st);
+        uint64_t totals[kCounts];
+        if (int e = dual1_decode_size(c, n, dmsg, doff, nullptr, base, ds, dst, totals)) return e;
+        // the offsets and the statuses leave on every return
         for (int j = 0; j < kQT; j++)
-            MH_HIP(hipMemcpyAsync(offs[j], so + (uint64_t)j * (n + 1), (n + 1) * 8,
-                                  hipMemcpyDeviceToHost, st));
-        uint64_t tot[2] = {0, 0};  // nested terms, metadata bytes
-        MH_HIP(hipMemcpyAsync(&tot[0], so + (uint64_t)kQT * (n + 1) + n, 8, hipMemcpyDeviceToHost, st));
-        MH_HIP(hipMemcpyAsync(&tot[1], so + (uint64_t)kMd * (n + 1) + n, 8, hipMemcpyDeviceToHost, st));
-        MH_HIP(hipMemcpyAsync(status, base + b_st, n * 4, hipMemcpyDeviceToHost, st));
-        MH_HIP(hipStreamSynchronize(st));
+            MH_HIP(hipMemcpyAsync(offs[j], ds.off(base, j, n), (n + 1) * 8, hipMemcpyDeviceToHost, st));
+        MH_HIP(hipMemcpyAsync(status, dst, n * 4, hipMemcpyDeviceToHost, st));
+        out->nested_proofs = totals[kQ];
+        out->nested_terms = totals[kQT];
         const uint64_t caps[kCounts - 1] = {out->incl_cap,   out->cons_cap,        out->last_cap,
                                             out->linear_cap, out->advance_cap,     out->advance_incl_cap,
                                             out->advance_incl_terms_cap};
         uint8_t *hterms[5] = {out->incl_terms, out->cons_terms, out->last_terms, out->linear_terms,
                               out->advance_terms};
-        uint64_t totals[kCounts - 1];
-        for (int j = 0; j < kQT; j++) totals[j] = offs[j][n];
-        totals[kQT] = tot[0];
-        out->nested_proofs = totals[kQ];
-        out->nested_terms = totals[kQT];
-        for (int j = 0; j < kCounts - 1; j++)
-            if (totals[j] > caps[j]) return MH_ERR_BUFFER_TOO_SMALL;
+        int rc = MH_OK;  // a short capacity is reported before a missing pointer
         for (int j = 0; j < 5; j++)
-            if (totals[j] && !hterms[j]) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (totals[kQT] && !out->advance_incl_terms) return MH_ERR_ILLEGAL_ARGUMENTS;
-        // device term area: the five lists, the nested terms, the nested offsets
-        uint64_t tpos[6], tall = 0;
-        for (int j = 0; j < 5; j++) {
-            tpos[j] = tall;
-            tall += totals[j];
+            if (totals[j] && !hterms[j]) rc = MH_ERR_ILLEGAL_ARGUMENTS;
+        if (totals[kQT] && !out->advance_incl_terms) rc = MH_ERR_ILLEGAL_ARGUMENTS;
+        for (int j = 0; j < kCounts - 1; j++)
+            if (totals[j] > caps[j]) rc = MH_ERR_BUFFER_TOO_SMALL;
+        if (rc) {  // the copies above still write the caller's arrays
+            MH_HIP(hipStreamSynchronize(st));
+            return rc;
         }
-        tpos[5] = tall;
-        tall += totals[kQT];
-        const uint64_t nq = totals[kQ];
+        Layout T;
+        const Dual1Terms dterms = dual1_decode_terms(T, totals);
         DevBuf &tb = c->s_tree;
-        MH_HIP(tb.ensure(tall * 32 + (nq + 1) * 8 + 8));
+        MH_HIP(tb.ensure(T.total + 8));
         uint8_t *dt = tb.as<uint8_t>();
-        uint64_t *dq = (uint64_t *)(dt + tall * 32);
         Dual1Arrays o;
-        for (int j = 0; j < kCounts; j++) o.off[j] = so + (uint64_t)j * (n + 1);
-        for (int j = 0; j < 5; j++) o.terms[j] = dt + tpos[j] * 32;
-        o.qterms = dt + tpos[5] * 32;
-        o.qoff = dq;
-        o.src_hdr = (mh_tx_header *)(base + b_h);
-        o.tgt_hdr = o.src_hdr + n;
-        o.md_blob = base + b_md;
-        o.tbl_alh = base + b_tba;
-        o.has_lin = base + b_flags;
-        o.has_adv = base + b_flags + n;
-        o.lin_src = (uint64_t *)(base + b_ls);
-        o.lin_tgt = o.lin_src + n;
-        hipLaunchKernelGGL(k_pbd_dual1<true>, dim3(grid), dim3(256), 0, st, n, dmsg,
-                           (const uint64_t *)(base + b_off), nullptr, nullptr, o,
-                           (int32_t *)(base + b_st));
-        MH_HIP(hipGetLastError());
+        if (int e = dual1_decode_write(c, n, dmsg, doff, nullptr, base, ds, dt, dterms, dst, o))
+            return e;
         const size_t hb = n * sizeof(mh_tx_header);
-        MH_HIP(hipMemcpyAsync(out->src_hdr, base + b_h, hb, hipMemcpyDeviceToHost, st));
-        MH_HIP(hipMemcpyAsync(out->tgt_hdr, base + b_h + hb, hb, hipMemcpyDeviceToHost, st));
-        if (tot[1]) MH_HIP(hipMemcpyAsync(out->md_blob, base + b_md, tot[1], hipMemcpyDeviceToHost, st));
-        MH_HIP(hipMemcpyAsync(out->target_bl_tx_alh, base + b_tba, n * 32, hipMemcpyDeviceToHost, st));
-        MH_HIP(hipMemcpyAsync(out->has_linear, base + b_flags, n, hipMemcpyDeviceToHost, st));
-        MH_HIP(hipMemcpyAsync(out->has_advance, base + b_flags + n, n, hipMemcpyDeviceToHost, st));
-        MH_HIP(hipMemcpyAsync(out->linear_src, base + b_ls, n * 8, hipMemcpyDeviceToHost, st));
-        MH_HIP(hipMemcpyAsync(out->linear_tgt, base + b_ls + n * 8, n * 8, hipMemcpyDeviceToHost, st));
+        MH_HIP(hipMemcpyAsync(out->src_hdr, o.src_hdr, hb, hipMemcpyDeviceToHost, st));
+        MH_HIP(hipMemcpyAsync(out->tgt_hdr, o.tgt_hdr, hb, hipMemcpyDeviceToHost, st));
+        if (totals[kMd])
+            MH_HIP(hipMemcpyAsync(out->md_blob, o.md_blob, totals[kMd], hipMemcpyDeviceToHost, st));
+        MH_HIP(hipMemcpyAsync(out->target_bl_tx_alh, o.tbl_alh, n * 32, hipMemcpyDeviceToHost, st));
+        MH_HIP(hipMemcpyAsync(out->has_linear, o.has_lin, n, hipMemcpyDeviceToHost, st));
+        MH_HIP(hipMemcpyAsync(out->has_advance, o.has_adv, n, hipMemcpyDeviceToHost, st));
+        MH_HIP(hipMemcpyAsync(out->linear_src, o.lin_src, n * 8, hipMemcpyDeviceToHost, st));
+        MH_HIP(hipMemcpyAsync(out->linear_tgt, o.lin_tgt, n * 8, hipMemcpyDeviceToHost, st));
         for (int j = 0; j < 5; j++)
             if (totals[j])
-                MH_HIP(hipMemcpyAsync(hterms[j], dt + tpos[j] * 32, totals[j] * 32,
-                                      hipMemcpyDeviceToHost, st));
+                MH_HIP(hipMemcpyAsync(hterms[j], o.terms[j], totals[j] * 32, hipMemcpyDeviceToHost, st));
         if (totals[kQT])
-            MH_HIP(hipMemcpyAsync(out->advance_incl_terms, dt + tpos[5] * 32, totals[kQT] * 32,
+            MH_HIP(hipMemcpyAsync(out->advance_incl_terms, o.qterms, totals[kQT] * 32,
                                   hipMemcpyDeviceToHost, st));
-        MH_HIP(hipMemcpyAsync(out->advance_incl_off, dq, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
+        MH_HIP(hipMemcpyAsync(out->advance_incl_off, o.qoff, (totals[kQ] + 1) * 8,
+                              hipMemcpyDeviceToHost, st));
         MH_HIP(hipStreamSynchronize(st));
         return MH_OK;
     });
@@ -1293,17 +1303,14 @@ extern "C" int mh_verify_dual_proof_v2_pb_batch(mh_ctx *c, uint64_t n, const uin
         if (!c) return MH_ERR_ILLEGAL_ARGUMENTS;
         if (n == 0) return MH_OK;
         PbChunkFrame F;
-        if (int e = F.open(c, n, msgs, msg_off, src, tgt, src_alh, tgt_alh, status != nullptr))
-            return e;
+        if (int e = F.open(c, n, msgs, msg_off, src && tgt && src_alh && tgt_alh && status)) return e;
         const std::vector<uint64_t> &cut = F.cut;
         const uint64_t m0 = F.m0, mb = F.mb, chunk_bytes = F.chunk_bytes;
         const int nch = F.nch;
         hipStream_t st = c->stream;
         uint64_t max_nk = 0;
         for (int k = 0; k < nch; k++) max_nk = std::max(max_nk, cut[k + 1] - cut[k]);
-        size_t scan_bytes = 0;
-        MH_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const uint64_t *)nullptr,
-                                                (uint64_t *)nullptr, (int)max_nk, st));
+        const size_t scan_bytes = pb_scan_temp_bytes(max_nk);
         Layout L;
         // caller arrays (xa: the source Alh values, then the target ones), the
         // decode's arrays (per-chunk offset arrays hold n_k + 1 entries at
@@ -1324,7 +1331,12 @@ extern "C" int mh_verify_dual_proof_v2_pb_batch(mh_ctx *c, uint64_t n, const uin
         MH_HIP(tb.ensure(std::max<uint64_t>(std::min(mb, chunk_bytes) / 34 + 64, 1) * 32));
         uint8_t *base = c->s_tx.as<uint8_t>();
         ChunkCopier cc(c);
-        F.fill(cc, base + b_msg, base + b_off, base + b_src, base + b_tgt, base + b_xa);
+        F.fill(cc, base + b_msg,
+               {{base + b_off, msg_off, (n + 1) * 8},
+                {base + b_src, src, n * 8},
+                {base + b_tgt, tgt, n * 8},
+                {base + b_xa, src_alh, n * 32},
+                {base + b_xa + n * 32, tgt_alh, n * 32}});
         MH_HIP(cc.start());
         const uint8_t *dmsg = base + b_msg - m0;
         int32_t *dst_all = (int32_t *)(base + b_st);
@@ -1345,21 +1357,14 @@ extern "C" int mh_verify_dual_proof_v2_pb_batch(mh_ctx *c, uint64_t n, const uin
                                nullptr, nullptr, nullptr, nullptr, nullptr, dst);
             MH_HIP(hipGetLastError());
             uint64_t *outs[3] = {io, co, mo};
-            for (int q = 0; q < 3; q++) {
-                MH_HIP(hipMemsetAsync(outs[q], 0, 8, st));
-                size_t sb = scan_bytes;
-                MH_HIP(hipcub::DeviceScan::InclusiveSum(base + b_scan, sb,
-                                                        (const uint64_t *)(cnt + q * n + lo),
-                                                        outs[q] + 1, (int)nk, st));
-            }
+            for (int q = 0; q < 3; q++)
+                MH_HIP(scan_offsets_u64(st, nk, cnt + q * n + lo, outs[q], base + b_scan, scan_bytes));
             // the chunk's term totals size its term area: one small read-back
             // (waits for this chunk only; later chunks keep copying), stored
             // by a kernel into pinned memory rather than copied by the DMA
             // engine that is busy with the next chunks
             volatile uint64_t *tot = c->p_small.as<volatile uint64_t>();
-            hipLaunchKernelGGL(k_put2_host, dim3(1), dim3(64), 0, st, io + nk, co + nk,
-                               (uint64_t *)c->p_small.p);
-            MH_HIP(hipGetLastError());
+            MH_HIP(launch_put2_host(st, io + nk, co + nk, (uint64_t *)c->p_small.p));
             MH_HIP(hipStreamSynchronize(st));
             MH_HIP(tb.ensure(std::max<uint64_t>(tot[0] + tot[1], 1) * 32));
             uint8_t *dti = tb.as<uint8_t>(), *dtc = dti + tot[0] * 32;
@@ -1384,11 +1389,12 @@ extern "C" int mh_verify_dual_proof_v2_pb_batch(mh_ctx *c, uint64_t n, const uin
 }
 
 // DualProof (v1) straight from the wire: the chunk frame of the V2 call above
-// (PbChunkFrame), the decode of mh_dual_proof_pb_decode_batch into device
+// (PbChunkFrame) and its groups, the decode stage of
+// mh_dual_proof_pb_decode_batch (dual1_decode_size / _write) into device
 // scratch, then dual_proof_v1_core (capi_tx.hip) -- the verifier behind
 // mh_verify_dual_proof_batch too -- over the decoded arrays, with
 // kDp1V0MetadataDropped: a v0 header's metadata bytes are not hashed.  The
-// decode scratch is sized for the largest group of chunks (below) and reused
+// decode scratch is sized for the largest group of chunks and reused
 // group after group (one compute stream orders them); only status and ok
 // leave the device.
 extern "C" int mh_verify_dual_proof_pb_batch(mh_ctx *c, uint64_t n, const uint8_t *msgs,
@@ -1399,102 +1405,48 @@ extern "C" int mh_verify_dual_proof_pb_batch(mh_ctx *c, uint64_t n, const uint8_
         if (!c) return MH_ERR_ILLEGAL_ARGUMENTS;
         if (n == 0) return MH_OK;
         PbChunkFrame F;
-        if (int e = F.open(c, n, msgs, msg_off, src, tgt, src_alh, tgt_alh, status && ok)) return e;
-        const std::vector<uint64_t> &cut = F.cut;
-        const uint64_t m0 = F.m0, mb = F.mb;
+        if (int e = F.open(c, n, msgs, msg_off, src && tgt && src_alh && tgt_alh && status && ok))
+            return e;
         hipStream_t st = c->stream;
-        Timer *tm = c->tm();
-        // consecutive chunks decoded and verified by one set of launches
-        const std::vector<int> gcut = F.groups();
-        const int ng = (int)gcut.size() - 1;
-        uint64_t M = 0;  // proofs of the largest group
-        for (int g = 0; g < ng; g++) M = std::max(M, cut[gcut[g + 1]] - cut[gcut[g]]);
-        size_t scan_bytes = 0;
-        MH_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const uint64_t *)nullptr,
-                                                (uint64_t *)nullptr, (int)M, st));
+        F.group();
         Layout L;
         // the caller's arrays and the results, whole; then one group's decode
-        const uint64_t b_msg = L.add(mb + 16), b_off = L.add((n + 1) * 8), b_src = L.add(n * 8),
+        const uint64_t b_msg = L.add(F.mb + 16), b_off = L.add((n + 1) * 8), b_src = L.add(n * 8),
                        b_tgt = L.add(n * 8), b_xa = L.add(2 * n * 32), b_st = L.add(n * 4),
                        b_ok = L.add(n);
-        const uint64_t b_cnt = L.add(kCounts * M * 8), b_so = L.add(kCounts * (M + 1) * 8),
-                       b_scan = L.add(scan_bytes), b_h = L.add(2 * M * sizeof(mh_tx_header)),
-                       b_md = L.add(2 * M * (uint64_t)kMdSlot), b_tba = L.add(M * 32),
-                       b_flags = L.add(2 * M), b_lsrc = L.add(2 * M * 8);
+        const Dual1Scratch ds = dual1_decode_scratch(L, F.group_n);
         MH_HIP(c->s_tx.ensure(L.total));
         uint8_t *base = c->s_tx.as<uint8_t>();
-        auto U = [&](uint64_t off) { return (uint64_t *)(base + off); };
         ChunkCopier cc(c);
-        F.fill(cc, base + b_msg, base + b_off, base + b_src, base + b_tgt, base + b_xa);
+        F.fill(cc, base + b_msg,
+               {{base + b_off, msg_off, (n + 1) * 8},
+                {base + b_src, src, n * 8},
+                {base + b_tgt, tgt, n * 8},
+                {base + b_xa, src_alh, n * 32},
+                {base + b_xa + n * 32, tgt_alh, n * 32}});
         MH_HIP(cc.start());
-        const uint8_t *dmsg = base + b_msg - m0;
+        const uint8_t *dmsg = base + b_msg - F.m0;
         int32_t *dst_all = (int32_t *)(base + b_st);
-        uint64_t *cnt = U(b_cnt), *so = U(b_so);
         DevBuf &tb = c->s_tree;
-        for (int g = 0; g < ng; g++) {
-            for (int k = gcut[g]; k < gcut[g + 1]; k++) {
-                MH_HIP(cc.wait(k));
-                MH_HIP(hipStreamWaitEvent(st, c->ev_chunks[k], 0));
-            }
-            const uint64_t lo = cut[gcut[g]], nk = cut[gcut[g + 1]] - lo;
-            const unsigned grid = (unsigned)((nk + 255) / 256);
+        for (int g = 0; g < F.ng; g++) {
+            uint64_t lo, nk;
+            if (int e = F.wait_group(c, cc, g, lo, nk)) return e;
             const uint64_t *doff = (const uint64_t *)(base + b_off) + lo;
             int32_t *dst = dst_all + lo;
-            // decode: validate + count, the eight scans
-            {
-                TimerScope ts(tm, "pbd_dual1_size", st);
-                hipLaunchKernelGGL(k_pbd_dual1<false>, dim3(grid), dim3(256), 0, st, nk, dmsg, doff,
-                                   nullptr, cnt, Dual1Arrays{}, dst);
-                MH_HIP(hipGetLastError());
-            }
-            for (int j = 0; j < kCounts; j++) {
-                uint64_t *sj = so + (uint64_t)j * (nk + 1);
-                MH_HIP(hipMemsetAsync(sj, 0, 8, st));
-                size_t sb = scan_bytes;
-                MH_HIP(hipcub::DeviceScan::InclusiveSum(base + b_scan, sb,
-                                                        (const uint64_t *)(cnt + j * nk), sj + 1,
-                                                        (int)nk, st));
-            }
-            // the group's seven totals size its term area: stored by a kernel
-            // into pinned memory (the DMA engine is busy with the next chunks)
-            volatile uint64_t *tot = c->p_small.as<volatile uint64_t>();
-            hipLaunchKernelGGL(k_put7_host, dim3(1), dim3(64), 0, st, so, nk,
-                               (uint64_t *)c->p_small.p);
-            MH_HIP(hipGetLastError());
-            MH_HIP(hipStreamSynchronize(st));
-            uint64_t totals[kMd];
-            for (int j = 0; j < kMd; j++) totals[j] = tot[j];
-            // term area: the five lists, the nested terms and their offsets;
-            // then the verifier's scratch
+            uint64_t totals[kCounts];
+            if (int e = dual1_decode_size(c, nk, dmsg, doff, nullptr, base, ds, dst, totals)) return e;
+            // the term area, then the verifier's scratch
             const uint64_t Q = totals[kQ];
             Layout T;
-            uint64_t t_terms[5];
-            for (int j = 0; j < 5; j++) t_terms[j] = T.add(totals[j] * 32);
-            const uint64_t t_qt = T.add(totals[kQT] * 32), t_qo = T.add((Q + 1) * 8),
-                           t_core = T.add(dual_proof_v1_scratch_bytes(nk, Q));
+            const Dual1Terms dterms = dual1_decode_terms(T, totals);
+            const uint64_t t_core = T.add(dual_proof_v1_scratch_bytes(nk, Q));
             MH_HIP(tb.ensure(T.total + 8));
             uint8_t *dt = tb.as<uint8_t>();
             Dual1Arrays o;
-            for (int j = 0; j < kCounts; j++) o.off[j] = so + (uint64_t)j * (nk + 1);
-            for (int j = 0; j < 5; j++) o.terms[j] = dt + t_terms[j];
-            o.qterms = dt + t_qt;
-            o.qoff = (uint64_t *)(dt + t_qo);
-            o.src_hdr = (mh_tx_header *)(base + b_h);
-            o.tgt_hdr = o.src_hdr + nk;
-            o.md_blob = base + b_md;
-            o.tbl_alh = base + b_tba;
-            o.has_lin = base + b_flags;
-            o.has_adv = base + b_flags + nk;
-            o.lin_src = U(b_lsrc);
-            o.lin_tgt = o.lin_src + nk;
-            {
-                TimerScope ts(tm, "pbd_dual1_write", st);
-                hipLaunchKernelGGL(k_pbd_dual1<true>, dim3(grid), dim3(256), 0, st, nk, dmsg, doff,
-                                   nullptr, nullptr, o, dst);
-                MH_HIP(hipGetLastError());
-            }
+            if (int e = dual1_decode_write(c, nk, dmsg, doff, nullptr, base, ds, dt, dterms, dst, o))
+                return e;
             // VerifyDualProof (verification.go:127-235)
-            if (int e = dual_proof_v1_core(st, tm, nk, o, (const uint64_t *)(base + b_src) + lo,
+            if (int e = dual_proof_v1_core(st, c->tm(), nk, o, (const uint64_t *)(base + b_src) + lo,
                                            (const uint64_t *)(base + b_tgt) + lo,
                                            base + b_xa + lo * 32, base + b_xa + (n + lo) * 32, dst,
                                            2 * nk * (uint64_t)kMdSlot, kDp1V0MetadataDropped, Q,

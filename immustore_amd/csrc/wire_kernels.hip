@@ -699,11 +699,15 @@ uint64_t pb_scratch_bytes(uint64_t n) {
 
 // in[0..n) -> out[0..n] with out[0] = 0, out[k+1] = in[0] + ... + in[k]
 hipError_t scan_offsets_u64(hipStream_t st, uint64_t n, const uint64_t *in, uint64_t *out,
-                            uint8_t *temp) {
+                            uint8_t *temp, size_t temp_bytes) {
     if (hipError_t e = hipMemsetAsync(out, 0, sizeof(uint64_t), st)) return e;
     if (!n) return hipSuccess;
-    size_t bytes = pb_scan_temp_bytes(n);
-    return hipcub::DeviceScan::InclusiveSum(temp, bytes, in, out + 1, (int)n, st);
+    return hipcub::DeviceScan::InclusiveSum(temp, temp_bytes, in, out + 1, (int)n, st);
+}
+
+hipError_t scan_offsets_u64(hipStream_t st, uint64_t n, const uint64_t *in, uint64_t *out,
+                            uint8_t *temp) {
+    return scan_offsets_u64(st, n, in, out, temp, pb_scan_temp_bytes(n));
 }
 
 // sizes -> off[0..n] (off[0] = 0)

@@ -677,6 +677,80 @@ def test_dual_v1_decode_random_vs_protobuf(m, ctx, wire):
     assert seen == {0, 2, 14}
 
 
+def test_dual_v1_decode_capacity(m, ctx, wire):
+    """mh_dual_proof_pb_decode_batch's capacity contract, straight through the
+    C ABI: any of the seven capacities short -> BUFFER_TOO_SMALL with the six
+    n + 1 offset arrays, the statuses and the two nested totals filled as the
+    exact call fills them (the size query); a non-empty list without its term
+    pointer -> ILLEGAL_ARGUMENTS; the exact call equals decode_dual_proof_pb;
+    n = 0 -> OK with zero offsets."""
+    import ctypes as C
+    from immustore_amd import _native as N
+    from immustore_amd import txlayer
+    from immustore_amd.merkle import _addr
+    rng = np.random.default_rng(11)
+    raws = [random_dual_v1_msg(wire, rng) for _ in range(40)]
+    n = len(raws)
+    off = np.zeros(n + 1, np.uint64)
+    off[1:] = np.cumsum([len(x) for x in raws])
+    buf = np.frombuffer(b"".join(raws), np.uint8).copy()
+    est = [expect_v1(wire, r)[0] for r in raws]
+    assert buf.size == 35011 and est.count(0) == 33 and est.count(2) == 7
+    L, h = N.load(), ctx.handle
+    lists = ("incl", "cons", "last", "linear", "advance")
+    offs = [t + "_off" for t in lists] + ["advance_incl_first"]
+    ptrs = [f for f, _ in txlayer._DualProofDecoded._fields_[:21]]
+
+    def call(caps, null=None, nn=n):
+        """caps: the seven capacities in the struct's order -> (rc, arrays, struct)"""
+        a = {"src_hdr": np.zeros(n, txlayer.TX_HEADER), "tgt_hdr": np.zeros(n, txlayer.TX_HEADER),
+             "md_blob": np.zeros(2 * n * 268, np.uint8),
+             "target_bl_tx_alh": np.zeros((n, 32), np.uint8), "has_linear": np.zeros(n, np.uint8),
+             "linear_src": np.zeros(n, np.uint64), "linear_tgt": np.zeros(n, np.uint64),
+             "has_advance": np.zeros(n, np.uint8),
+             "advance_incl_off": np.full(caps[5] + 1, 0xee, np.uint64)}
+        for f in offs:
+            a[f] = np.full(n + 1, 0xee, np.uint64)
+        for t, cap in zip(lists + ("advance_incl",), caps[:5] + caps[6:]):
+            a[t + "_terms"] = np.zeros((max(cap, 1), 32), np.uint8)
+        a["status"] = np.full(n, -1, np.int32)
+        d = txlayer._DualProofDecoded(*[None if f == null else _addr(a[f]) for f in ptrs], *caps,
+                                      0xee, 0xee)
+        rc = L.mh_dual_proof_pb_decode_batch(h, nn, _addr(buf), _addr(off), C.byref(d),
+                                             _addr(a["status"]))
+        return rc, a, d
+
+    def sizes(a, d):
+        return ([a[f].tolist() for f in offs], a["status"].tolist(), int(d.nested_proofs),
+                int(d.nested_terms))
+
+    rc, a0, d0 = call((0,) * 7)
+    assert rc == N.MH_ERR_BUFFER_TOO_SMALL
+    exact = tuple(int(a0[f][n]) for f in offs) + (int(d0.nested_terms),)
+    assert int(d0.nested_proofs) == exact[5]
+    assert exact == (214, 237, 203, 161, 51, 49, 117) and all(x > 0 for x in exact)
+    rc, ax, dx = call(exact)
+    assert rc == 0
+    want = sizes(ax, dx)
+    assert sizes(a0, d0) == want and want[1] == est
+    for k in range(7):
+        short = exact[:k] + (exact[k] - 1,) + exact[k + 1:]
+        rc, a, d = call(short)
+        assert rc == N.MH_ERR_BUFFER_TOO_SMALL, k
+        assert sizes(a, d) == want, k
+    assert call(exact, null="cons_terms")[0] == N.MH_ERR_ILLEGAL_ARGUMENTS
+    # a short capacity is reported before a missing pointer
+    assert call((exact[0] - 1,) + exact[1:], null="cons_terms")[0] == N.MH_ERR_BUFFER_TOO_SMALL
+    st, ref = txlayer.decode_dual_proof_pb(raws, ctx=ctx)
+    assert st.tolist() == ax["status"].tolist()
+    assert set(ref) == set(ptrs)
+    for f in ptrs:
+        assert np.array_equal(ax[f][:len(ref[f])], ref[f]), f
+    rc, a, d = call((0,) * 7, nn=0)
+    assert rc == 0 and all(int(a[f][0]) == 0 for f in offs) and int(a["advance_incl_off"][0]) == 0
+    assert int(d.nested_proofs) == 0 and int(d.nested_terms) == 0
+
+
 # ------------------------------------------- DualProofV2 from the wire, verified
 def _compose(txlayer, msgs, S, T, SA, TA, ctx):
     """decode, then mh_verify_dual_proof_v2_batch, with Go's v0 rule (a v0
