@@ -1,5 +1,6 @@
 // capi_internal.hpp -- host-side objects shared by the C-ABI translation
-// units (capi.hip: htree / ahtree handles; capi_tx.hip: tx layer).
+// units (capi.hip: htree / ahtree handles; capi_tx.hip: tx layer;
+// txlog_hop.hip, capi_txlog.hip, capi_clog.hip: the tx-log read path).
 #pragma once
 #include <algorithm>
 #include <condition_variable>
@@ -192,7 +193,6 @@ struct mh_ctx {
     DevBuf s_txpatch;     // the same + canonical metadata records (rare)
     DevBuf s_clog;        // mh_txlog_validate_clog's per-record arrays
     uint64_t clog_wmax = 0;  // the widest record of its last resident call (the next launch's guess)
-    PinBuf p_tx;          // its pinned staging of the parsed index arrays
     // mh_txlog_validate's groups (one per copy chunk): device arrays and
     // pinned index staging of each, kept across calls
     std::deque<DevBuf> s_txg;
@@ -204,7 +204,6 @@ struct mh_ctx {
     hipStream_t copy_stream = nullptr;
     hipStream_t copy_stream2 = nullptr;  // a second copy lane (ChunkCopier)
     hipStream_t d2h_stream = nullptr;  // device->host results of an early part of a call
-    hipStream_t stream2 = nullptr;     // a second compute stream (tx-log groups)
     hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
     DevBuf s_chunk[2];
     std::vector<hipEvent_t> ev_chunks;  // one per chunk of a pipelined call (arrivals)
@@ -216,7 +215,6 @@ struct mh_ctx {
         hipError_t e = hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking);
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&copy_stream2, hipStreamNonBlocking);
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&d2h_stream, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking);
         for (int k = 0; k < 2 && e == hipSuccess; k++) {
             e = hipEventCreateWithFlags(&ev_copied[k], hipEventDisableTiming);
             if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_done[k], hipEventDisableTiming);
@@ -233,11 +231,17 @@ struct mh_ctx {
         if (copy_stream) hipStreamDestroy(copy_stream);
         if (copy_stream2) hipStreamDestroy(copy_stream2);
         if (d2h_stream) hipStreamDestroy(d2h_stream);
-        if (stream2) hipStreamDestroy(stream2);
     }
 };
 
-// ---- the tx-log record hop (capi_tx.hip), shared with the multi-device call
+// the n-byte big-endian number at p (n <= 8)
+inline uint64_t be_at(const uint8_t *p, int n) {
+    uint64_t v = 0;
+    for (int i = 0; i < n; i++) v = (v << 8) | p[i];
+    return v;
+}
+
+// ---- the tx-log record hop (txlog_hop.hip), shared with the multi-device call
 // Records of one stretch of a tx log (the structure readHeader / readEntry
 // read, tx.go:419-603; no hashing).
 // Per record: where it starts, where its stored Alh is, its entry count and
@@ -276,14 +280,85 @@ struct HopLimits {
 
 // The whole hop of a run of records (no headers kept), as mh_txlog_validate
 // runs it: out.R, out.P, out.rc (the structural status), out.end (consumed).
-void txlog_hop(const uint8_t *buf, uint64_t len, uint32_t max_entries, uint32_t max_key_len,
-               uint64_t max_txs, HopOut &out);
-// mh_txlog_validate with the record structure parsed already (pre: every
-// record of [buf, buf + len) with offsets relative to buf, patches indexed by
-// record, rc MH_OK, end == len): no host hop in the call.
+void txlog_hop(const uint8_t *buf, uint64_t len, uint64_t max_txs, const HopLimits &lim, HopOut &out,
+               bool want_headers = false);
+// Records [r0, r1) of a finished hop as a log of their own: their bytes start
+// at all->R[r0].rec == base, and all->P[p0] is the first patch of a record
+// >= r0.  Offsets and patch indices are rebased as the view is read.
+struct HopView {
+    const HopOut *all;
+    size_t r0, r1, p0;
+    uint64_t base;
+};
+// mh_txlog_validate with the record structure parsed already (capi_txlog.hip;
+// pre: every record of [buf, buf + len), the last one ending at len): no host
+// hop in the call.
 int txlog_validate_parsed(mh_ctx *c, const uint8_t *buf, uint64_t len, uint32_t max_entries,
-                          uint32_t max_key_len, const HopOut &pre, mh_tx_header *hdrs_out,
+                          uint32_t max_key_len, const HopView &pre, mh_tx_header *hdrs_out,
                           uint8_t *alh_out, int32_t *status_out);
+
+// ---- pieces the read-path calls share (capi_txlog.hip; capi_clog.hip)
+// The caller's output arrays of a read-path call (each may be null), and where
+// their records can be stored to: the one place that knows about pinned host
+// memory, device memory and the kernels' 8-byte aligned headers.
+struct TxlogOutputs {
+    int32_t *status = nullptr;
+    uint8_t *alh = nullptr;
+    mh_tx_header *hdrs = nullptr;
+    // Records [t0, t0 + nt) of each array as a kernel can store them: the
+    // device alias of pinned host memory (one registration or allocation, word
+    // aligned), the array itself when it is device memory (device_ok; bad when
+    // its range is not inside one allocation), else null.  all: every array
+    // the caller passed has such an address; aligned(): the headers' is a
+    // multiple of 8 (the kernels store them as 64-bit words).
+    struct Dst {
+        uint32_t *st = nullptr, *alh = nullptr, *hd = nullptr;
+        bool st_dev = false, alh_dev = false, hd_dev = false, bad = false, all = false;
+        bool aligned() const { return ((uintptr_t)hd & 7) == 0; }
+        // what a kernel stores its results through
+        TxlogHostOut host_out() const { return TxlogHostOut{st, alh, reinterpret_cast<uint64_t *>(hd), 0}; }
+    };
+    Dst dst(uint64_t t0, uint64_t nt, bool device_ok) const;
+    // "copy down": records [t0, t0 + nt) of the arrays d has no store address
+    // for, from the device arrays st_src / alh_src / hd_src (indexed from t0)
+    int copy_down(hipStream_t st, uint64_t t0, uint64_t nt, const Dst &d, const void *st_src,
+                  const void *alh_src, const void *hd_src) const;
+    // one re-validated record t (the cLog host fallback): into the outputs that
+    // are device memory by copies on st, into those in host memory directly
+    // (after the call's last wait)
+    int put_device(hipStream_t st, const Dst &d, uint64_t t, const int32_t *s, const uint8_t *a,
+                   const mh_tx_header *h) const;
+    void put_host(const Dst &d, uint64_t t, int32_t s, const uint8_t *a, const mh_tx_header &h) const;
+};
+
+// Once a call's kernels are queued they may store into the caller's pinned or
+// device arrays, and copies read the caller's log: every exit (errors
+// included) waits for the streams listed here, so nothing touches caller
+// memory after return.  Cleared once the call's own final waits ran.
+struct StreamGuard {
+    std::vector<hipStream_t> streams;
+    ~StreamGuard() {
+        for (hipStream_t s : streams) hipStreamSynchronize(s);
+    }
+};
+
+// The device range [p, p + bytes) lies in one allocation of the current
+// device (hipMemGetAddressRange), or the address is not device memory at all.
+bool dev_range(const void *p, uint64_t bytes);
+// The copy chunks of a log of len bytes at `log`: chunk k is bytes [cut[k],
+// cut[k + 1]).  One chunk for a resident log or one below 16 MiB, else
+// txlog_weights() (5 : 2 : 1) for a pinned log and 3 : 1 for a pageable one,
+// cut at multiples of 4 KiB.  *pinned: the whole log lies in one pinned
+// allocation.
+std::vector<uint64_t> txlog_chunk_cuts(const uint8_t *log, uint64_t len, bool resident, bool *pinned);
+// mh_txlog_validate's body.  c->mu MUST be held by the caller (the public
+// calls take it; the cLog call's host fallback holds it already).  buf: the
+// log in host memory (the hop parses it); dlog: the same bytes already
+// resident on the device (no copy; nullptr: copied from buf in chunks);
+// parsed: the records, when the caller has hopped already (else nullptr).
+int txlog_validate_core(mh_ctx *c, const uint8_t *buf, const uint8_t *dlog, uint64_t len,
+                        HopLimits lim, uint64_t max_txs, uint64_t *ntx_out, uint64_t *consumed_out,
+                        const TxlogOutputs &out, const HopView *parsed);
 
 // Host-to-device copies of a call cut into chunks, issued from one helper
 // thread (or two, chunk k on lane k % 2) onto the context's copy stream(s)

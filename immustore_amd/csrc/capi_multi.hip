@@ -1028,7 +1028,7 @@ extern "C" int mh_multi_txlog_validate(mh_multi *m, const uint8_t *buf, uint64_t
                                      ntx_out, consumed_out, hdrs_out, alh_out, status_out);
         if (len && !buf) return MH_ERR_ILLEGAL_ARGUMENTS;
         HopOut all;
-        txlog_hop(buf, len, max_entries, max_key_len, max_txs, all);
+        txlog_hop(buf, len, max_txs, HopLimits{max_entries, max_key_len}, all);
         const uint64_t cnt = all.R.size(), used = all.end;
         const int rc = all.rc;
         if (ntx_out) *ntx_out = cnt;
@@ -1048,22 +1048,13 @@ extern "C" int mh_multi_txlog_validate(mh_multi *m, const uint8_t *buf, uint64_t
             }
             t[d] = std::max(t[d - 1], std::min(lo, cnt));
         }
-        // each part's records and patches, rebased to the part
-        std::vector<HopOut> part(K);
+        // each part's records and patches: a range of the parse, rebased to
+        // the part as it is read
+        std::vector<HopView> part(K);
         size_t p = 0;
         for (int d = 0; d < K; d++) {
-            const uint64_t t0 = t[d], t1 = t[d + 1], b0 = start(t0);
-            HopOut &o = part[d];
-            o.R.reserve(t1 - t0);
-            for (uint64_t k = t0; k < t1; k++)
-                o.R.push_back(HopRec{all.R[k].rec - b0, all.R[k].alh - b0, all.R[k].nent, 0});
-            for (; p < all.P.size() && all.P[p].rec < t1; p++) {
-                HopPatch pt = all.P[p];
-                pt.rec -= t0;
-                o.P.push_back(std::move(pt));
-            }
-            o.rc = MH_OK;
-            o.end = start(t1) - b0;
+            part[d] = HopView{&all, t[d], t[d + 1], p, start(t[d])};
+            while (p < all.P.size() && all.P[p].rec < t[d + 1]) p++;
         }
         std::lock_guard<std::mutex> lk(m->mu);
         const int st = per_device(K, [&](int d) -> int {

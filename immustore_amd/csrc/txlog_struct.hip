@@ -86,7 +86,7 @@ __device__ __forceinline__ int tx_md_check(const uint8_t *md, uint32_t ml, bool 
 }
 
 // the record at p read within [p, lim), exactly hop_record's checks in its
-// order (capi_tx.hip, tx.go:419-588); eof: no record there (id 0 or no room
+// order (txlog_hop.hip, tx.go:419-588); eof: no record there (id 0 or no room
 // for an id)
 __device__ int struct_record(const uint8_t *buf, uint64_t p, uint64_t lim, uint32_t max_entries,
                              uint32_t max_key_len, uint32_t &nent, uint64_t &alh, bool &eof,

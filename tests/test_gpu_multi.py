@@ -393,6 +393,17 @@ def test_multi_txlog_validate_vs_single_and_oracle(m, orc, fixtures, devices):
     from tx_util import _bulk_txlog, metadata_logs
     nc = b"".join(r for n, r in metadata_logs(orc) if n == "noncanonical_sealed_canonical")
     logs += [nc * 40 + logs[0] + nc * 40, _bulk_txlog(rng, 9000)[0]]
+    if devices == [0, 0]:
+        # parts of >= 16 MiB: the pre-parsed records of a part are read over
+        # several copy-chunk phases -- pageable (two phases, 3 : 1), pinned
+        # (three, 5 : 2 : 1), and with re-encoded metadata in front (patches,
+        # which end the early groups)
+        import torch
+        big = _bulk_txlog(rng, 12000)[0]
+        assert len(big) >= (33 << 20), len(big)
+        pin = torch.empty(len(big), dtype=torch.uint8).pin_memory()
+        pin.numpy()[:] = np.frombuffer(big, np.uint8)
+        logs += [big, pin.numpy(), nc * 50 + big]
     ctx = m.Context(0)
     md = MultiDevice(devices)
     try:
@@ -402,7 +413,7 @@ def test_multi_txlog_validate_vs_single_and_oracle(m, orc, fixtures, devices):
             assert got[:3] == single[:3], (devices, k)
             assert np.array_equal(got[3], single[3]) and np.array_equal(got[4], single[4])
             assert np.array_equal(got[5], single[5]), (devices, k)
-            o = orc.txlog_validate(raw)
+            o = orc.txlog_validate(bytes(raw))
             assert got[:3] == (o[0], o[1], o[2]) and np.array_equal(got[4], o[3][:got[1]])
             assert list(got[5]) == list(o[4][:got[1]])
     finally:

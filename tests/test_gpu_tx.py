@@ -713,6 +713,11 @@ def test_txlog_validate_resident_vs_host_path(m, ctx, orc, monkeypatch, kern):
     for p in rng.integers(0, len(bad), 20):
         bad[int(p)] ^= 0x08
     logs.append(bytes(bad))
+    # a transaction wider than the fused kernels take (> 64 entries): the chain
+    # and the tree plan run over the uploaded host copy
+    wide = _synthetic_txlog(rng, 20, orc, max_entries=300)
+    assert (m.txlog_validate(wide, ctx=ctx)[3]["nentries"] > 64).any()
+    logs.append(wide)
     cap = 1000
     pin = (torch.empty(cap * TX_HEADER.itemsize, dtype=torch.uint8).pin_memory().numpy().view(TX_HEADER),
            torch.empty(cap * 32, dtype=torch.uint8).pin_memory().numpy().reshape(cap, 32),
