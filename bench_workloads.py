@@ -423,7 +423,7 @@ def distributed_main(a):
 def make_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--workload", choices=["c3", "c5", "c2e2e", "txlog", "commit", "wire", "ragged", "document",
-                                          "values", "c3range", "dualv1", "dualv1verify"],
+                                          "values", "c3range", "dualv1", "dualv1verify", "replicate"],
                    required=True)
     p.add_argument("--logs", action="store_true",
                    help="c3: also write the pLog / cLog appendable records (8(f) row 4)")
@@ -450,6 +450,9 @@ def make_parser():
                    help="dualv1: header pairs (default 10^5); dualv1verify: random pairs "
                         "(default: as many as make about 1 GiB of messages)")
     p.add_argument("--v1-depth", type=int, default=20, help="dualv1: log2 of the appends")
+    p.add_argument("--repl-txs", type=int, default=4096, help="replicate: exported txs")
+    p.add_argument("--repl-leaves", type=int, default=10 ** 5,
+                   help="replicate: leaves of the follower's tree before the batch")
     return p
 
 
@@ -879,6 +882,151 @@ def c3range(a, m, N, L, ctx, dev, sync):
             "value": round(M / t / 1e6, 1), "unit": "M appends/s", "ms": res,
             "device_bytes": {"range": int(rng_buf.numel()), "full_dlog": int(full.numel())},
             "identical_to_full_dlog_append": same}
+
+
+def replicate(a, m, N, L, ctx, sync):
+    """The follower's catch-up: --repl-txs consecutive exported txs (v1,
+    --tx-entries entries of 8-byte keys and --vlen-byte values, pinned) onto a
+    tree of --repl-leaves leaves through mh_replicate_tx_batch, next to today's
+    path over the same txs already repacked into CSR arrays (no host parse):
+    mh_precommit_batch + mh_tx_alh_batch + mh_ahtree_append_batch."""
+    import ctypes as C
+    import struct
+    import numpy as np
+    import torch
+    from immustore_amd.replicate import _Batch, REPLICATED_ENTRY
+    from immustore_amd.txlayer import TX_HEADER
+    orc = _oracle()
+    orc.use_shani(True)
+    ntx, per, vlen, P = a.repl_txs, a.tx_entries, a.vlen, a.repl_leaves
+    n = ntx * per
+    pin = lambda nbytes: torch.empty(max(nbytes, 1), dtype=torch.uint8).pin_memory().numpy()  # noqa: E731
+    rng = np.random.default_rng(24)
+    # the follower's tree: P random Alh values, on the device and in the oracle
+    old = rng.integers(0, 256, (P, 32), dtype=np.uint8)
+    ot = orc.AHtree(P + ntx)
+    if P:
+        ot.append_batch(old)
+    prev = old[-1].tobytes() if P else orc.sha256(b"")
+    # the primary's txs: hVal, Eh (oracle, 16 threads), then the chain
+    vals = pin(n * vlen)
+    vals[:] = rng.integers(0, 256, n * vlen, dtype=np.uint8)
+    keys = pin(n * 8)
+    keys[:] = np.frombuffer(np.arange(n, dtype=">u8").tobytes(), np.uint8)
+    pin_u64 = lambda x: pin(x.nbytes).view(np.uint64)  # noqa: E731
+    csr = dict(tx_off=np.arange(0, n + 1, per, dtype=np.uint64), keys=keys,
+               key_off=np.arange(0, 8 * n + 1, 8, dtype=np.uint64), vals=vals,
+               val_off=np.arange(0, vlen * n + 1, vlen, dtype=np.uint64))
+    for k in ("tx_off", "key_off", "val_off"):
+        q = pin_u64(csr[k])
+        q[:] = csr[k]
+        csr[k] = q
+    _, eh, st = orc.precommit_batch(1, nthreads=16, **csr)
+    assert not st.any()
+    hdrs = pin(ntx * TX_HEADER.itemsize).view(TX_HEADER)
+    hdrs[:] = np.zeros(ntx, TX_HEADER)
+    alhs = np.zeros((ntx, 32), np.uint8)
+    blobs, cur = [], prev
+    for k in range(ntx):
+        txid = P + k + 1
+        bl = txid - 1
+        bl_root = ot.root_at(bl)[1] if bl else bytes(32)
+        ts = 1700000000 + k
+        s_, inner = orc.tx_inner_hash(ts, 1, b"", per, eh[k].tobytes(), bl, bl_root)
+        alh = orc.tx_alh(txid, cur, inner)
+        h = hdrs[k]
+        h["id"], h["ts"], h["bl_tx_id"], h["version"], h["nentries"] = txid, ts, bl, 1, per
+        h["bl_root"] = np.frombuffer(bl_root, np.uint8)
+        h["prev_alh"] = np.frombuffer(cur, np.uint8)
+        h["eh"] = eh[k]
+        hb = struct.pack(">Q", txid) + cur + struct.pack(">qHHI", ts, 1, 0, per) + eh[k].tobytes() + \
+            struct.pack(">Q", bl) + bl_root
+        ents = b"".join(struct.pack(">H", 8) + keys[8 * e:8 * e + 8].tobytes() + struct.pack(">HI", 0, vlen)
+                        + vals[vlen * e:vlen * (e + 1)].tobytes() for e in range(k * per, (k + 1) * per))
+        blobs.append(struct.pack(">I", len(hb)) + hb + ents + b"\x00\x01\x00")
+        ot.append(alh)
+        alhs[k] = np.frombuffer(alh, np.uint8)
+        cur = alh
+    flat = b"".join(blobs)
+    txs = pin(len(flat))
+    txs[:] = np.frombuffer(flat, np.uint8)
+    off = pin_u64(np.zeros(ntx + 1, np.uint64))
+    off[0] = 0
+    off[1:] = np.cumsum([len(x) for x in blobs], dtype=np.uint64)
+    root_want = ot.root_at(P + ntx)[1]
+
+    t = m.AHtree(ctx)
+    if P:
+        t.append_batch(old)
+    # ---- the new call, every output pinned
+    b = _Batch()
+    b.n, b.txs, b.tx_off = ntx, txs.ctypes.data, off.ctypes.data
+    b.max_entries, b.max_key_len, b.max_value_len, b.flags = 1024, 1024, 1 << 25, 0
+    b.prev_alh[:] = list(prev)
+    o_st = pin(ntx * 4).view(np.int32)
+    o_hd = pin(ntx * TX_HEADER.itemsize)
+    o_md = pin(ntx * 268)
+    o_alh = pin(ntx * 32)
+    o_eo = pin_u64(np.zeros(ntx + 1, np.uint64))
+    o_en = pin(n * REPLICATED_ENTRY.itemsize)
+    o_hv = pin(n * 32)
+    acc = C.c_uint64(0)
+
+    def step_new():
+        N.check(L.mh_ahtree_reset_size(t.handle, P))
+        N.check(L.mh_replicate_tx_batch(t.handle, C.addressof(b), o_st.ctypes.data, C.byref(acc),
+                                        o_hd.ctypes.data, o_md.ctypes.data, o_alh.ctypes.data,
+                                        o_eo.ctypes.data, o_en.ctypes.data, n, o_hv.ctypes.data))
+        assert acc.value == ntx
+
+    # ---- today's path: three calls with a host round trip between each
+    pipe = m.CommitPipe(ctx)
+    hv = pin(n * 32).reshape(n, 32)
+    eh_o = pin(ntx * 32).reshape(ntx, 32)
+    inner_o = pin(ntx * 32)
+    alh_o = pin(ntx * 32)
+    md1 = np.zeros(1, np.uint8)
+
+    def step_old():
+        N.check(L.mh_ahtree_reset_size(t.handle, P))
+        _, _, st_ = pipe.precommit_csr(1, expect_eh=eh, hvals_out=hv, eh_out=eh_o, **csr)
+        assert not st_.any()
+        N.check(L.mh_tx_alh_batch(ctx.handle, ntx, hdrs.ctypes.data, md1.ctypes.data, 0,
+                                  inner_o.ctypes.data, alh_o.ctypes.data))
+        N.check(L.mh_ahtree_append_batch(t.handle, alh_o.ctypes.data, ntx, 32, None))
+
+    prewarm(step_new, sync, a.prewarm)
+    t_old1 = timed(step_old, a.steps, a.warmup, sync)
+    t_new = timed_k(ctx, step_new, a.steps, a.warmup, sync)
+    names = ("repl_struct_size", "repl_struct_write", "repl_set", "repl_leaf", "leaf_for", "repl_alh",
+             "repl_verdict", "aht")
+    kd = {k: round(ctx.timing(k)[0] / (a.steps + a.warmup), 3) for k in names}
+    n_new, root_new = t.root()
+    ok_new = bool(n_new == P + ntx and root_new == root_want and not o_st.any()
+                  and o_alh.tobytes() == alhs.tobytes())
+    t_old2 = timed(step_old, a.steps, a.warmup, sync)
+    n_old, root_old = t.root()
+    ok_old = bool(n_old == P + ntx and root_old == root_want)
+    t_old = min(t_old1, t_old2)
+    pipe.close()
+    t.close()
+    gib = len(flat) / 2 ** 30
+    return {"metric": "ReplicateTx of a run of exported txs in one call: parse, hash, verdicts, append",
+            "value": round(ntx / t_new), "unit": "txs/s", "ms_per_step": round(t_new * 1e3, 3),
+            "gib_per_s": round(gib / t_new, 3),
+            "three_calls": {"ms": round(t_old * 1e3, 3), "ms_before": round(t_old1 * 1e3, 3),
+                            "ms_after": round(t_old2 * 1e3, 3),
+                            "note": "mh_precommit_batch + mh_tx_alh_batch + mh_ahtree_append_batch over "
+                                    "the same txs already repacked (pinned CSR arrays): no host parse, "
+                                    "no BlRoot / PrevAlh / id checks"},
+            "three_calls_over_new": round(t_old / t_new, 3),
+            "kernel_ms": kd,
+            "config": {"txs": ntx, "entries_per_tx": per, "key_len": 8, "value_len": vlen,
+                       "version": 1, "tree_leaves": P, "blob_bytes": len(flat), "pinned": True},
+            "root_check": {"ok": ok_new and ok_old, "new_call": ok_new, "three_calls": ok_old,
+                           "root": root_want.hex(),
+                           "against": "oracle AHtree over the same Alh values; the call's statuses "
+                                      "and Alh values"}}
 
 
 def run_single(a):
@@ -1325,6 +1473,8 @@ def run_single(a):
         out = values(a, m, N, L, ctx, dev, sync)
     elif a.workload == "c3range":
         out = c3range(a, m, N, L, ctx, dev, sync)
+    elif a.workload == "replicate":
+        out = replicate(a, m, N, L, ctx, sync)
     elif a.workload == "c2e2e":
         n, vlen, klen = 1 << 20, 1024, 8
         hv = torch.empty(n * vlen, dtype=torch.uint8).pin_memory()

@@ -24,5 +24,7 @@ from .txlayer import (TX_HEADER, tx_alh_batch, htree_build_many, verify_linear_p
                       txlog_validate)
 from . import commit
 from .commit import CommitPipe, EntrySpec
+from . import replicate
+from .replicate import REPLICATED_ENTRY, replicate_tx_batch
 
 __all__ = [n for n in dir() if not n.startswith("_")]

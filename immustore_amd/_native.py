@@ -41,6 +41,18 @@ MH_ERR_INVALID_PROOF_ENTRY = 22
 MH_ERR_COLLECTIVE = 23
 MH_ERR_CORRUPTED_TX_DATA = 24
 MH_ERR_TX_NOT_FOUND = 25
+MH_ERR_NEWER_VERSION_OR_CORRUPTED = 26
+MH_ERR_ILLEGAL_TRUNCATION_ARGUMENT = 27
+MH_ERR_NULL_KEY = 28
+MH_ERR_MAX_KEY_LEN_EXCEEDED = 29
+MH_ERR_MAX_VALUE_LEN_EXCEEDED = 30
+MH_ERR_MAX_TX_ENTRIES_EXCEEDED = 31
+MH_ERR_TX_ALREADY_COMMITTED = 32
+MH_ERR_TX_OUT_OF_ORDER = 33
+MH_ERR_TX_NOT_REACHED = 34
+
+MH_REPL_SKIP_INTEGRITY = 1
+MH_REPL_DRY_RUN = 2
 
 MH_AHT_INCLUSION = 0
 MH_AHT_CONSISTENCY = 1
@@ -157,6 +169,42 @@ class ErrTxNotFound(MerkleError):
     """store.ErrTxNotFound (immustore.go:85)"""
 
 
+class ErrNewerVersionOrCorruptedData(MerkleError):
+    """store.ErrNewerVersionOrCorruptedData (immustore.go:91)"""
+
+
+class ErrIllegalTruncationArgument(ErrIllegalArguments):
+    """store.ErrIllegalTruncationArgument (immustore.go:111)"""
+
+
+class ErrNullKey(MerkleError):
+    """store.ErrNullKey (immustore.go:60)"""
+
+
+class ErrMaxKeyLenExceeded(MerkleError):
+    """store.ErrMaxKeyLenExceeded (immustore.go:61)"""
+
+
+class ErrMaxValueLenExceeded(MerkleError):
+    """store.ErrMaxValueLenExceeded (immustore.go:62)"""
+
+
+class ErrMaxTxEntriesLimitExceeded(MerkleError):
+    """store.ErrMaxTxEntriesLimitExceeded (immustore.go:59)"""
+
+
+class ErrTxAlreadyCommitted(MerkleError):
+    """store.ErrTxAlreadyCommitted (immustore.go:58)"""
+
+
+class ErrTxOutOfOrder(MerkleError):
+    """"attempt to commit a tx in wrong order" (immustore.go:1716)"""
+
+
+class ErrTxNotReached(MerkleError):
+    """a tx behind the first refused one of its mh_replicate_tx_batch"""
+
+
 class HipError(MerkleError):
     pass
 
@@ -187,6 +235,15 @@ _ERRORS = {
     MH_ERR_COLLECTIVE: ErrCollective,
     MH_ERR_CORRUPTED_TX_DATA: ErrCorruptedTxData,
     MH_ERR_TX_NOT_FOUND: ErrTxNotFound,
+    MH_ERR_NEWER_VERSION_OR_CORRUPTED: ErrNewerVersionOrCorruptedData,
+    MH_ERR_ILLEGAL_TRUNCATION_ARGUMENT: ErrIllegalTruncationArgument,
+    MH_ERR_NULL_KEY: ErrNullKey,
+    MH_ERR_MAX_KEY_LEN_EXCEEDED: ErrMaxKeyLenExceeded,
+    MH_ERR_MAX_VALUE_LEN_EXCEEDED: ErrMaxValueLenExceeded,
+    MH_ERR_MAX_TX_ENTRIES_EXCEEDED: ErrMaxTxEntriesLimitExceeded,
+    MH_ERR_TX_ALREADY_COMMITTED: ErrTxAlreadyCommitted,
+    MH_ERR_TX_OUT_OF_ORDER: ErrTxOutOfOrder,
+    MH_ERR_TX_NOT_REACHED: ErrTxNotReached,
 }
 
 vp = C.c_void_p
@@ -339,6 +396,7 @@ SIGNATURES = {
                                          C.POINTER(u64), vp, u8p, vp]),
     "mh_txlog_validate_clog": (i32, [vp, vp, u64, vp, u64, u32, u32, u32, vp, vp, vp,
                                      C.POINTER(u64), C.POINTER(u64)]),
+    "mh_replicate_tx_batch": (i32, [vp, vp, vp, C.POINTER(u64), vp, u8p, u8p, vp, vp, u64, u8p]),
     "mh_commit_pipe_new": (i32, [vp, u64, C.POINTER(vp)]),
     "mh_commit_pipe_free": (i32, [vp]),
     "mh_precommit_batch": (i32, [vp, i32, u64, u64, vp, u8p, vp, u8p, vp, u8p, vp, u8p, u8p, u8p,

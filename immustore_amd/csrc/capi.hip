@@ -73,6 +73,16 @@ extern "C" const char *mh_status_string(int st) {
         case MH_ERR_COLLECTIVE: return "RCCL collective failed or RCCL not available";
         case MH_ERR_CORRUPTED_TX_DATA: return "tx data is corrupted";
         case MH_ERR_TX_NOT_FOUND: return "tx not found";
+        case MH_ERR_NEWER_VERSION_OR_CORRUPTED:
+            return "tx created with a newer version or data is corrupted";
+        case MH_ERR_ILLEGAL_TRUNCATION_ARGUMENT: return "illegal arguments: invalid truncation info";
+        case MH_ERR_NULL_KEY: return "null key";
+        case MH_ERR_MAX_KEY_LEN_EXCEEDED: return "max key length exceeded";
+        case MH_ERR_MAX_VALUE_LEN_EXCEEDED: return "max value length exceeded";
+        case MH_ERR_MAX_TX_ENTRIES_EXCEEDED: return "max number of entries per tx exceeded";
+        case MH_ERR_TX_ALREADY_COMMITTED: return "tx already committed";
+        case MH_ERR_TX_OUT_OF_ORDER: return "unexpected error: attempt to commit a tx in wrong order";
+        case MH_ERR_TX_NOT_REACHED: return "tx not reached: an earlier tx of the batch was refused";
         default: return st < 0 ? hipGetErrorString((hipError_t)(-st)) : "unknown status";
     }
 }
@@ -1038,7 +1048,7 @@ extern "C" int mh_ahtree_free(mh_ahtree *t) {
     });
 }
 
-static int aht_reserve(mh_ahtree *t, uint64_t new_size) {
+int aht_reserve(mh_ahtree *t, uint64_t new_size) {
     const uint64_t need = ahtree_nodes_upto(new_size) * 32;
     if (need <= t->dlog.cap && t->dlog.p) return MH_OK;
     uint64_t cap = std::max<uint64_t>(need, t->dlog.cap * 2);

@@ -188,7 +188,8 @@ struct mh_ctx {
     DevBuf s_edge;        // ahtree frontier of a ranged append (64 x 32 B)
     DevBuf s_sort;        // length-class sort of ragged messages (varlen_kernels.hip)
     DevBuf s_tx, s_tree;  // tx layer (capi_tx.hip)
-    DevBuf s_ventry;      // inclusion terms of VerifiableGet answers (capi_entry.hip)
+    DevBuf s_ventry;      // inclusion terms of VerifiableGet answers (capi_entry.hip); a group's
+                          // entry arrays of mh_replicate_tx_batch (capi_repl.hip)
     DevBuf s_txlog;       // raw tx-log bytes of mh_txlog_validate
     DevBuf s_txpatch;     // the same + canonical metadata records (rare)
     DevBuf s_clog;        // mh_txlog_validate_clog's per-record arrays
@@ -677,6 +678,10 @@ struct mh_ahtree {
     DevBuf dlog, in, roots, idx, out, ctr;
     DevBuf w_in, w_out;  // wire formats (capi_wire.hip)
 };
+
+// room in t's dLog for new_size leaves (capi.hip; t->mu held): may move the
+// dLog, keeping the nodes of t->size leaves
+int aht_reserve(mh_ahtree *t, uint64_t new_size);
 
 // Header preconditions shared by every entry point that reads headers.
 inline int check_header(const mh_tx_header &h, uint64_t md_blob_len, bool have_blob) {

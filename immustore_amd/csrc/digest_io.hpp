@@ -115,6 +115,13 @@ __device__ __forceinline__ uint32_t be_keep(int64_t v) {  // the first v bytes o
     return v >= 4 ? 0xffffffffu : (v <= 0 ? 0u : (0xffffffffu << (32 - 8 * (int)v)));
 }
 
+// byte k (0..15) of a 16-byte big-endian register prefix |= b
+__device__ __forceinline__ void put_pre(uint32_t (&pre)[4], uint32_t k, uint32_t b) {
+    const uint32_t x = b << (24 - 8 * (k & 3));
+#pragma unroll
+    for (uint32_t w = 0; w < 4; w++) pre[w] |= (k >> 2) == w ? x : 0u;
+}
+
 template <bool SUF>
 __device__ inline void sha256_seg(const uint32_t pre[4], uint32_t plen, const uint8_t *p,
                                   uint64_t len, const uint32_t suf[8], uint32_t out[8]) {

@@ -404,6 +404,53 @@ hipError_t launch_vtx_leaf(hipStream_t st, Timer *tm, uint64_t T, const VtxVerif
 hipError_t launch_vtx_spec(hipStream_t st, Timer *tm, uint64_t T, const VtxVerify &v);
 hipError_t launch_vtx_answer(hipStream_t st, Timer *tm, const VtxVerify &v);
 
+// ---- exported txs replicated onto a follower's tree (capi_repl.hip,
+// repl_kernels.hip).  One group of nk txs: tx p is msgs[tx_off[p] ..
+// tx_off[p + 1]) (msgs biased like the callers' offsets); per-tx arrays are
+// the group's slices, per-entry arrays start at the group's first entry.
+struct ReplLimits {
+    uint32_t max_entries, max_key_len, max_value_len, flags;
+};
+struct ReplGroup {
+    uint64_t nk, first;         // txs of the group, the batch index of its first
+    const uint8_t *msgs;
+    const uint64_t *tx_off;     // nk + 1
+    int32_t *status;            // the envelope-through-Eh verdict
+    uint64_t *cnt;              // size pass: entries of a tx that parsed, else 0
+    const uint64_t *ent_off;    // nk + 1, scanned from cnt
+    mh_tx_header *hdr;          // write pass; md_off = (first + p) x kMdSlot
+    uint8_t *md_blob;           // the whole batch's (canonical TxMetadata.Bytes())
+    uint8_t *trunc;             // write pass: the trailer says truncated
+    mh_replicated_entry *ents;  // write pass
+    uint8_t *dup;               // an earlier entry of the tx has the same key
+    uint8_t *dig, *hv;          // entry digests / hVal, 32 bytes an entry
+    const uint8_t *roots;       // built Eh of every tx (after build_many_dev)
+    uint8_t *alh;               // Alh of a tx with status MH_OK, else zeros
+    uint8_t *alh_msg;           // nk x kTxInnerStride bytes of scratch
+};
+// the wire grammar: write = false status and cnt, write = true hdr, md_blob,
+// trunc, ents of the txs still MH_OK
+hipError_t launch_repl_struct(hipStream_t st, Timer *tm, bool write, const ReplGroup &g);
+// dup, then OngoingTx.set / validateAgainst / validateEntries per tx (status)
+hipError_t launch_repl_set(hipStream_t st, Timer *tm, uint64_t T, const ReplGroup &g,
+                           const ReplLimits &lim);
+// hVal and entry digest of every entry of a tx still MH_OK
+hipError_t launch_repl_leaf(hipStream_t st, Timer *tm, uint64_t T, const ReplGroup &g);
+// Eh against the exported one, hdr.eh = the built one, the Alh
+hipError_t launch_repl_alh(hipStream_t st, Timer *tm, const ReplGroup &g, const ReplLimits &lim);
+// The chain and linking verdicts of all n txs against dlog = the P resident
+// leaves + the n candidate Alh leaves: full[k] = local[k], or the id / BlRoot
+// / PrevAlh verdict had every earlier tx been accepted; then a = the first k
+// with full[k] != MH_OK (n: none) into *first_bad, and every tx behind a gets
+// local[k] or MH_ERR_TX_NOT_REACHED.
+struct ReplPrev {
+    uint8_t alh[32];
+};
+hipError_t launch_repl_verdict(hipStream_t st, Timer *tm, uint64_t n, const int32_t *local,
+                               const mh_tx_header *hdr, const uint8_t *alh, const uint8_t *dlog,
+                               uint64_t P, const ReplPrev &prev, int32_t *full,
+                               unsigned long long *first_bad);
+
 __device__ __forceinline__ void copy32_a8(uint8_t *d, const uint8_t *s) {  // both 8-byte aligned
     const uint2 *a = (const uint2 *)s;
     uint2 *b = (uint2 *)d;

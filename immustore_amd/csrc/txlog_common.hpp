@@ -1,5 +1,6 @@
 // txlog_common.hpp -- device helpers shared by the fused a14 kernels
-// (txlog_wave.hip, txlog_lanes.hip, txlog_struct.hip): byte-order reads of the
+// (txlog_wave.hip, txlog_lanes.hip, txlog_struct.hip) and the exported-tx
+// reader (repl_kernels.hip): the metadata grammars, byte-order reads of the
 // raw tx-log records (tx.go:419-588 layout) and the entry-digest block builder
 // of TxEntryDigest_v1_1 / _v1_2 (tx.go:690-731) straight from the record.
 #pragma once
@@ -96,6 +97,58 @@ __device__ __forceinline__ void skip12_block(const uint8_t *p, uint32_t la, uint
         for (int j = 0; j < 20; j++) d[j] = qq[j];
     }
     skip12_words(d, al, la, b, nb, w);
+}
+
+// KVMetadata.unsafeReadFrom (kv_metadata.go:207-256): deleted(0),
+// expiresAt(1, 8 bytes), nonIndexable(2); an unknown code or a short
+// expiresAt is ErrCorruptedData.  Bytes() writes each attribute once in code
+// order, so the stored form is canonical iff its codes strictly increase.
+// Returns MH_OK / MH_ERR_CORRUPTED_DATA; *canon: the canonical form.
+__device__ __forceinline__ int kv_md_check(const uint8_t *md, uint32_t ml, bool *canon) {
+    if (ml > MH_MAX_KV_METADATA_LEN) return MH_ERR_CORRUPTED_DATA;
+    int last = -1;
+    bool inc = true;
+    for (uint32_t i = 0; i < ml;) {
+        const uint32_t code = md[i++];
+        if (code == 1) {
+            if (ml - i < 8) return MH_ERR_CORRUPTED_DATA;
+            i += 8;
+        } else if (code > 2) {
+            return MH_ERR_CORRUPTED_DATA;
+        }
+        inc &= (int)code > last;
+        last = (int)code;
+    }
+    *canon = inc;
+    return MH_OK;
+}
+
+// TxMetadata.ReadFrom (tx_metadata.go:145-193): truncatedUptoTx(0, 8 bytes),
+// extra(1, BE16 length + up to 256 bytes); canonical iff the codes strictly
+// increase (Bytes() writes each once, in code order)
+__device__ __forceinline__ int tx_md_check(const uint8_t *md, uint32_t ml, bool *canon) {
+    if (ml > MH_MAX_TX_METADATA_LEN) return MH_ERR_CORRUPTED_DATA;
+    int last = -1;
+    bool inc = true;
+    for (uint32_t i = 0; i < ml;) {
+        const uint32_t code = md[i++];
+        if (code == 0) {
+            if (ml - i < 8) return MH_ERR_CORRUPTED_DATA;
+            i += 8;
+        } else if (code == 1) {
+            if (ml - i < 2) return MH_ERR_CORRUPTED_DATA;
+            const uint32_t el = rd_be16(md + i);
+            i += 2;
+            if (ml - i < el || el > 256) return MH_ERR_CORRUPTED_DATA;
+            i += el;
+        } else {
+            return MH_ERR_CORRUPTED_DATA;
+        }
+        inc &= (int)code > last;
+        last = (int)code;
+    }
+    *canon = inc;
+    return MH_OK;
 }
 
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t x) {

@@ -33,58 +33,6 @@ __device__ __forceinline__ uint64_t ld_be(const uint8_t *p, int n) {
     return v;
 }
 
-// KVMetadata.unsafeReadFrom (kv_metadata.go:207-256): deleted(0),
-// expiresAt(1, 8 bytes), nonIndexable(2); an unknown code or a short
-// expiresAt is ErrCorruptedData.  Bytes() writes each attribute once in code
-// order, so the stored form is canonical iff its codes strictly increase.
-// Returns MH_OK / MH_ERR_CORRUPTED_DATA; *canon: the canonical form.
-__device__ __forceinline__ int kv_md_check(const uint8_t *md, uint32_t ml, bool *canon) {
-    if (ml > MH_MAX_KV_METADATA_LEN) return MH_ERR_CORRUPTED_DATA;
-    int last = -1;
-    bool inc = true;
-    for (uint32_t i = 0; i < ml;) {
-        const uint32_t code = md[i++];
-        if (code == 1) {
-            if (ml - i < 8) return MH_ERR_CORRUPTED_DATA;
-            i += 8;
-        } else if (code > 2) {
-            return MH_ERR_CORRUPTED_DATA;
-        }
-        inc &= (int)code > last;
-        last = (int)code;
-    }
-    *canon = inc;
-    return MH_OK;
-}
-
-// TxMetadata.ReadFrom (tx_metadata.go:145-193): truncatedUptoTx(0, 8 bytes),
-// extra(1, BE16 length + up to 256 bytes); canonical iff the codes strictly
-// increase (Bytes() writes each once, in code order)
-__device__ __forceinline__ int tx_md_check(const uint8_t *md, uint32_t ml, bool *canon) {
-    if (ml > MH_MAX_TX_METADATA_LEN) return MH_ERR_CORRUPTED_DATA;
-    int last = -1;
-    bool inc = true;
-    for (uint32_t i = 0; i < ml;) {
-        const uint32_t code = md[i++];
-        if (code == 0) {
-            if (ml - i < 8) return MH_ERR_CORRUPTED_DATA;
-            i += 8;
-        } else if (code == 1) {
-            if (ml - i < 2) return MH_ERR_CORRUPTED_DATA;
-            const uint32_t el = rd_be16(md + i);
-            i += 2;
-            if (ml - i < el || el > 256) return MH_ERR_CORRUPTED_DATA;
-            i += el;
-        } else {
-            return MH_ERR_CORRUPTED_DATA;
-        }
-        inc &= (int)code > last;
-        last = (int)code;
-    }
-    *canon = inc;
-    return MH_OK;
-}
-
 // the record at p read within [p, lim), exactly hop_record's checks in its
 // order (txlog_hop.hip, tx.go:419-588); eof: no record there (id 0 or no room
 // for an id)

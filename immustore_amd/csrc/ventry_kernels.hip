@@ -28,13 +28,6 @@ namespace mh {
 
 namespace {
 
-// byte k (0..15) of a 16-byte big-endian register prefix |= b
-__device__ __forceinline__ void put_pre(uint32_t (&pre)[4], uint32_t k, uint32_t b) {
-    const uint32_t x = b << (24 - 8 * (k & 3));
-#pragma unroll
-    for (uint32_t w = 0; w < 4; w++) pre[w] |= (k >> 2) == w ? x : 0u;
-}
-
 __global__ __launch_bounds__(256) void k_ventry_verify(uint64_t n, VentryVerify v) {
     extern __shared__ uint32_t tab[];
     node_tab_init(tab);

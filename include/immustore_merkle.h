@@ -78,6 +78,18 @@ extern "C" {
                                          * mismatch, immustore.go:2416) */
 #define MH_ERR_TX_NOT_FOUND 25          /* store.ErrTxNotFound immustore.go:85 (a tx outside the
                                          * digest window of mh_*_dual_proof_pb_batch) */
+/* the follower's ReplicateTx (mh_replicate_tx_batch) */
+#define MH_ERR_NEWER_VERSION_OR_CORRUPTED 26 /* store.ErrNewerVersionOrCorruptedData immustore.go:91 */
+#define MH_ERR_ILLEGAL_TRUNCATION_ARGUMENT 27 /* store.ErrIllegalTruncationArgument immustore.go:111 */
+#define MH_ERR_NULL_KEY 28                /* store.ErrNullKey immustore.go:60 */
+#define MH_ERR_MAX_KEY_LEN_EXCEEDED 29    /* store.ErrMaxKeyLenExceeded immustore.go:61 */
+#define MH_ERR_MAX_VALUE_LEN_EXCEEDED 30  /* store.ErrMaxValueLenExceeded immustore.go:62 */
+#define MH_ERR_MAX_TX_ENTRIES_EXCEEDED 31 /* store.ErrMaxTxEntriesLimitExceeded immustore.go:59 */
+#define MH_ERR_TX_ALREADY_COMMITTED 32    /* store.ErrTxAlreadyCommitted immustore.go:58 */
+#define MH_ERR_TX_OUT_OF_ORDER 33         /* "attempt to commit a tx in wrong order"
+                                           * (store.ErrUnexpectedError immustore.go:89, :1716) */
+#define MH_ERR_TX_NOT_REACHED 34          /* a tx behind the first refused one of its batch (no Go
+                                           * sentinel: ReplicateTx is never called for it) */
 
 #define MH_MAX_TX_METADATA_LEN 268 /* maxTxMetadataLen tx_metadata.go:36-39 */
 #define MH_MAX_KV_METADATA_LEN 11  /* maxKVMetadataLen kv_metadata.go:41-43 */
@@ -692,6 +704,101 @@ int mh_precommit_batch(mh_commit_pipe *p, int version, uint64_t max_width, uint6
                        const uint64_t *val_off, const uint8_t *hval_override,
                        const uint8_t *use_override, const uint8_t *expect_eh, uint8_t *hvals_out,
                        uint8_t *eh_out, int32_t *status);
+
+/* ------------------------------------------------------------ follower path */
+/* ImmuStore.ReplicateTx (immustore.go:2772-2932) for a run of exported txs in
+ * one device pass: the bytes ExportTx wrote (:2621-2770) are parsed, every
+ * value hashed where it lies, each tx's hash tree rebuilt, and the precommit
+ * checks against the exported header (:1560-1755) decided against t, the
+ * follower's ahtree (size P = the last precommitted tx id; dLog resident).
+ * Tx k is txs[tx_off[k] .. tx_off[k+1]):
+ *   BE32 hdrLen | TxHeader.Bytes() (tx.go:103-164) |
+ *   per entry BE16 kLen | key | BE16 mdLen | md | BE32 vLen | value |
+ *   [BE16 tLen | tLen bytes, the first one 1 = values truncated]
+ * status[k] is what ReplicateTx would return for tx k had every earlier tx of
+ * the batch been applied; the first failing check decides, in Go's order:
+ *  envelope (:2773-2796): empty, < 4 bytes, < 4 + hdrLen bytes
+ *                                          -> MH_ERR_ILLEGAL_ARGUMENTS
+ *  TxHeader.ReadFrom (tx.go:166-247): < 124 bytes, id 0 -> ILLEGAL_ARGUMENTS;
+ *    v1 with len < i + mdLen + 4 or mdLen > 268, TxMetadata.ReadFrom errors
+ *    (as mh_txlog_validate) -> MH_ERR_CORRUPTED_DATA; version above 1 ->
+ *    MH_ERR_NEWER_VERSION_OR_CORRUPTED; NEntries 0, BlTxID >= id ->
+ *    ILLEGAL_ARGUMENTS.  A v1 header that ends inside Eh, BlTxID or BlRoot ->
+ *    ILLEGAL_ARGUMENTS (Go zero-fills a short Eh / BlRoot and panics on a
+ *    short BlTxID).  Bytes after BlRoot inside hdrLen are ignored, as in Go.
+ *  entries (:2806-2856), i the read position, len the blob's length:
+ *    len < i + 8; after kLen, len < i + 6 + kLen; after mdLen, len < i +
+ *    mdLen; after vLen, len < i + vLen -> ILLEGAL_ARGUMENTS (the first two
+ *    are looser than the bytes read: they count 6 bytes of lengths);
+ *    KVMetadata.unsafeReadFrom errors -> CORRUPTED_DATA; a vLen word that
+ *    would be read past the blob (metadata used up the slack; Go panics) ->
+ *    ILLEGAL_ARGUMENTS.
+ *  trailer (:2858-2881): none = not truncated; a 1-byte trailer (Go panics),
+ *    len < i + tLen, tLen == 0 (Go indexes v[0]) -> ILLEGAL_ARGUMENTS; v[0] >
+ *    1 -> MH_ERR_ILLEGAL_TRUNCATION_ARGUMENT; bytes left over ->
+ *    ILLEGAL_ARGUMENTS.
+ *  OngoingTx.set per entry in order (ongoing_tx.go:242-267): empty key ->
+ *    MH_ERR_NULL_KEY; key > max_key_len -> MH_ERR_MAX_KEY_LEN_EXCEEDED; value
+ *    > max_value_len (not truncated txs only) -> MH_ERR_MAX_VALUE_LEN_EXCEEDED;
+ *    a new key while more than max_entries are held ->
+ *    MH_ERR_MAX_TX_ENTRIES_EXCEEDED.  A key that repeats replaces the earlier
+ *    entry (compared byte for byte), so validateAgainst (:798) fails the tx
+ *    with ILLEGAL_ARGUMENTS; more than max_entries distinct keys ->
+ *    MAX_TX_ENTRIES_EXCEEDED (validateEntries immustore.go:3243).
+ *  hashing (:1620-1632): hVal = SHA256(value), or for a truncated tx the
+ *    first 32 bytes of "value", zero-padded (digest, :3666); the entry digest
+ *    of the header's version, KV metadata in its re-serialised form; KV
+ *    metadata under version 0 -> MH_ERR_METADATA_UNSUPPORTED; Eh = the root.
+ *  against the exported header (:1649-1722), R = P + k the id reached so far:
+ *    built Eh != hdr.Eh unless MH_REPL_SKIP_INTEGRITY -> ILLEGAL_ARGUMENTS;
+ *    id <= R -> MH_ERR_TX_ALREADY_COMMITTED; id > R + 1 ->
+ *    MH_ERR_TX_OUT_OF_ORDER (Go waits in WaitFor for the txs between and
+ *    fails "wrong order" only under concurrent writers: a batch cannot wait);
+ *    BlRoot != RootAt(BlTxID) over the P resident leaves plus the Alh of
+ *    every earlier tx of the batch (zeros for BlTxID 0) -> ILLEGAL_ARGUMENTS;
+ *    PrevAlh != the Alh reached so far (prev_alh, then the computed Alh of
+ *    the tx before) -> ILLEGAL_ARGUMENTS.
+ * The tx's Alh is TxHeader.Alh() over the header as precommitted: the built
+ * Eh, even when it was not compared.  *accepted = a, the length of the all-OK
+ * prefix; unless MH_REPL_DRY_RUN exactly those a Alh values are appended to t
+ * (the dLog bytes of mh_ahtree_append_batch), nothing else of t changes.  Tx a
+ * keeps its verdict; every later tx gets its own envelope-through-Eh verdict
+ * if that is an error, else MH_ERR_TX_NOT_REACHED.
+ * Outputs (host memory), for every tx whose bytes parsed (zeros otherwise):
+ * hdrs[k] with md_off into md_blob (slot k x MH_MAX_TX_METADATA_LEN, canonical
+ * bytes) and eh = the built Eh once the tx was hashed (else the exported one);
+ * alh[32 k] for a tx whose envelope-through-Eh verdict is MH_OK; ent_off[k] ..
+ * ent_off[k+1]) its entries in ents / hvals (md_off / md_len: the bytes as
+ * exported).  ents == NULL: no entry outputs.  ents_cap too small returns
+ * MH_ERR_BUFFER_TOO_SMALL with the needed count in ent_off[n], t untouched.
+ * NULL t / b / status / accepted, a non-monotonic tx_off, n >= 2^31 or above
+ * the md_blob frame (2 n x 268 < 2^32) return MH_ERR_ILLEGAL_ARGUMENTS before
+ * any device work.  The blobs go up once in the chunks and groups of
+ * mh_verify_dual_proof_pb_batch (MH_PB_CHUNK_MIB, MH_PB_GROUP_RATIO); the
+ * host never reads them. */
+#define MH_REPL_SKIP_INTEGRITY 1u /* ReplicateTx's skipIntegrityCheck: Eh is not compared (immustore.go:1650-1654) */
+#define MH_REPL_DRY_RUN        2u /* verdicts and outputs only; the tree is left as it was */
+
+typedef struct mh_replicated_entry { /* where entry e lies in its blob, offsets relative to txs */
+    uint64_t key_off, md_off, val_off;
+    uint32_t key_len, md_len, val_len, flags; /* flags bit 0: value truncated (val is the 32-byte hash) */
+} mh_replicated_entry;
+
+typedef struct mh_replicate_batch {
+    uint64_t n;              /* exported txs, in the order they are to be applied */
+    const uint8_t *txs;      /* the ExportTx byte strings back to back; host memory, pinned or pageable */
+    const uint64_t *tx_off;  /* n + 1 */
+    uint32_t max_entries, max_key_len, max_value_len; /* the store's options */
+    uint32_t flags;
+    uint8_t prev_alh[32];    /* the follower's inmemPrecommittedAlh (SHA256(nil) on an empty store, immustore.go:464) */
+} mh_replicate_batch;
+
+int mh_replicate_tx_batch(mh_ahtree *t, const mh_replicate_batch *b,
+                          int32_t *status /*n*/, uint64_t *accepted,
+                          mh_tx_header *hdrs /*n, nullable*/, uint8_t *md_blob /*n*MH_MAX_TX_METADATA_LEN, nullable*/,
+                          uint8_t *alh /*n*32, nullable*/,
+                          uint64_t *ent_off /*n+1, nullable*/, mh_replicated_entry *ents, uint64_t ents_cap,
+                          uint8_t *hvals /*ents_cap*32, nullable*/);
 
 /* Group commit of single transactions (the concurrent committers of
  * precommit, immustore.go:1620-1632: each hashes its own tx before taking the
