@@ -65,6 +65,55 @@ def test_host_index_math(lib_built, orc):
         assert m.nodes_upto(n) == orc.nodes_upto(n)
     # BASELINE C3: 10^7 appends -> 124,434,624 dLog digests
     assert m.nodes_upto(10 ** 7) == 124434624
+    # trees past 2^32 (the ranged appends' sizes): the library's 64-bit index
+    # math against the same sums in Python integers
+    import ctypes as C
+    from immustore_amd import _native as N
+    from ahtree_wide_util import WIDE_N0, in_domain, node_index, nodes_upto
+    L = N.load()
+    for n0 in WIDE_N0:
+        for n in (n0 - 1, n0, n0 + 1, n0 + 2100):
+            assert in_domain(n, 0)
+            assert L.mh_ahtree_nodes_upto(n) == nodes_upto(n), n
+            for lvl in (0, (n & -n).bit_length() - 1, 52):
+                assert L.mh_ahtree_node_index(n, lvl) == node_index(n, lvl), (n, lvl)
+        for total in (1, 300, 2100, 20011):
+            for K in (1, 2, 3, 8, 64):
+                assert _range_sizes(L, n0, total, K) == _range_sizes_py(L, n0, total, K), \
+                    (n0, total, K)
+    k, g = C.c_int(), C.c_int()
+    b = (C.c_uint64 * 5)()
+    assert L.mh_ahtree_range_plan(2 ** 64 - 10, 20, 4, C.byref(k), b, C.byref(g)) == \
+        N.MH_ERR_ILLEGAL_ARGUMENTS
+    s, w = C.c_uint64(), C.c_uint64()
+    assert L.mh_ahtree_range_sizes(2 ** 64 - 10, 20, 4, C.byref(s), C.byref(w)) == \
+        N.MH_ERR_ILLEGAL_ARGUMENTS
+
+
+_AHT_WORK_HEAD = 64 * 32 * 2 + 256  # kAhtWorkHead: peaks | frontier | work counter
+
+
+def _range_sizes(L, n0, total, K):
+    import ctypes as C
+    s, w = C.c_uint64(), C.c_uint64()
+    assert L.mh_ahtree_range_sizes(n0, total, K, C.byref(s), C.byref(w)) == 0
+    return s.value, w.value
+
+
+def _range_sizes_py(L, n0, total, K):
+    """(send_bytes, work_bytes) restated from the plan: Pmax send slots, the
+    largest count of pieces ending in one range, and one top-buffer slot per
+    piece-tree node of every level l with Pend >> l != 0, slots
+    N0 >> l .. Pend >> l."""
+    from immustore_amd.multi import ahtree_range_plan
+    k, b = ahtree_range_plan(n0, total, K)
+    pmax = max([1] + [(y >> k) - (x >> k) for x, y in zip(b, b[1:])])
+    N0, Pend = n0 >> k, b[-1] >> k
+    slots, lvl = 0, 0
+    while lvl < 64 - k and (Pend >> lvl):
+        slots += (Pend >> lvl) - (N0 >> lvl) + 1
+        lvl += 1
+    return pmax * 32, _AHT_WORK_HEAD + 32 * slots
 
 
 def test_no_silent_cpu_fallback(lib_built):

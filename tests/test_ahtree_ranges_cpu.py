@@ -16,6 +16,8 @@ import pytest
 from immustore_amd import _native as N
 from immustore_amd.multi import ahtree_range_plan, peaks_of
 
+from ahtree_wide_util import WIDE_N0, wide_case
+
 
 def _leaf(p):
     return hashlib.sha256(b"\x00" + bytes(p)).digest()
@@ -141,6 +143,37 @@ def test_ranged_model_vs_oracle(orc, K):
         got = model_append(n0, pk, pay[n0:n0 + total], K)
         want = ref[L.mh_ahtree_nodes_upto(n0):L.mh_ahtree_nodes_upto(n0 + total)].tobytes()
         assert got == want, (K, n0, total)
+
+
+_WIDE_MODEL_CASES = [(n0, total) for n0 in WIDE_N0 for total in (1, 129, 300)]
+_WIDE_MODEL_CASES.append((2 ** 40 + 12345, 2100))
+
+
+@pytest.mark.parametrize("K", [1, 2, 3, 8, 64])
+def test_ranged_model_vs_oracle_stream_wide(orc, K):
+    """The same model and the library's host code under it (mh_ahtree_range_plan,
+    mh_ahtree_nodes_upto, mh_ahtree_node_index) on trees past 2^32, where no
+    dLog can be held: fabricated peaks, and the oracle's peaks-only stream
+    (orc_ahtree_stream, ahtree.go:287-322) as the reference -- every digest of
+    every append, byte for byte.  The totals are small because the model is
+    plain Python; every n0 of WIDE_N0 is there."""
+    cases = list(_WIDE_MODEL_CASES)
+    if K == 64:
+        cases.append((2 ** 48 - 129, 5000))  # k = 2 and 64 ranges
+    for n0, total in cases:
+        c = wide_case(orc, n0, total)
+        got = model_append(n0, c.packed, c.pay, K)
+        assert got == c.want_rows.tobytes(), (K, n0, total)
+
+
+def test_range_plan_rejects_wrapping_sizes():
+    """n0 + total past 2^64 is an argument error, not a wrapped plan."""
+    import ctypes as C
+    L = N.load()
+    k, g = C.c_int(), C.c_int()
+    b = (C.c_uint64 * 5)()
+    st = L.mh_ahtree_range_plan(2 ** 64 - 10, 20, 4, C.byref(k), b, C.byref(g))
+    assert st == N.MH_ERR_ILLEGAL_ARGUMENTS
 
 
 def test_range_plan_properties():
