@@ -26,5 +26,7 @@ from . import commit
 from .commit import CommitPipe, EntrySpec
 from . import replicate
 from .replicate import REPLICATED_ENTRY, replicate_tx_batch
+from . import answers
+from .answers import ResidentStore, verifiable_answers, VerifiableTxByID, VerifiableGet
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -50,6 +50,8 @@ MH_ERR_MAX_TX_ENTRIES_EXCEEDED = 31
 MH_ERR_TX_ALREADY_COMMITTED = 32
 MH_ERR_TX_OUT_OF_ORDER = 33
 MH_ERR_TX_NOT_REACHED = 34
+MH_ERR_KEY_NOT_FOUND = 35
+MH_ANS_TX, MH_ANS_ENTRY = 0, 1
 
 MH_REPL_SKIP_INTEGRITY = 1
 MH_REPL_DRY_RUN = 2
@@ -205,6 +207,10 @@ class ErrTxNotReached(MerkleError):
     """a tx behind the first refused one of its mh_replicate_tx_batch"""
 
 
+class ErrKeyNotFound(MerkleError):
+    """store.ErrKeyNotFound from Tx.IndexOf (tx.go:361-368)"""
+
+
 class HipError(MerkleError):
     pass
 
@@ -244,6 +250,7 @@ _ERRORS = {
     MH_ERR_TX_ALREADY_COMMITTED: ErrTxAlreadyCommitted,
     MH_ERR_TX_OUT_OF_ORDER: ErrTxOutOfOrder,
     MH_ERR_TX_NOT_REACHED: ErrTxNotReached,
+    MH_ERR_KEY_NOT_FOUND: ErrKeyNotFound,
 }
 
 vp = C.c_void_p
@@ -397,6 +404,7 @@ SIGNATURES = {
     "mh_txlog_validate_clog": (i32, [vp, vp, u64, vp, u64, u32, u32, u32, vp, vp, vp,
                                      C.POINTER(u64), C.POINTER(u64)]),
     "mh_replicate_tx_batch": (i32, [vp, vp, vp, C.POINTER(u64), vp, u8p, u8p, vp, vp, u64, u8p]),
+    "mh_verifiable_answer_pb_batch": (i32, [vp, vp, vp, u8p, u64, vp, vp]),
     "mh_commit_pipe_new": (i32, [vp, u64, C.POINTER(vp)]),
     "mh_commit_pipe_free": (i32, [vp]),
     "mh_precommit_batch": (i32, [vp, i32, u64, u64, vp, u8p, vp, u8p, vp, u8p, vp, u8p, u8p, u8p,

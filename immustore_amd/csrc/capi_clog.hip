@@ -186,20 +186,19 @@ void clog_groups(const ClogState &s, const std::vector<uint64_t> &cut, std::vect
 
 }  // namespace
 
-extern "C" int mh_txlog_validate_clog(mh_ctx *c, const uint8_t *dlog, uint64_t len,
-                                      const uint8_t *clog, uint64_t ntx, uint32_t clog_entry_size,
-                                      uint32_t max_entries, uint32_t max_key_len,
-                                      mh_tx_header *hdrs_out, uint8_t *alh_out,
-                                      int32_t *status_out, uint64_t *nbad_out,
-                                      uint64_t *first_bad_out) {
-    return mh_guard([&]() -> int {
+// mh_txlog_validate_clog's body; c->mu MUST be held by the caller (the public
+// call takes it; mh_verifiable_answer_pb_batch holds it for its whole pass).
+int txlog_validate_clog_core(mh_ctx *c, const uint8_t *dlog, uint64_t len, const uint8_t *clog,
+                             uint64_t ntx, uint32_t clog_entry_size, uint32_t max_entries,
+                             uint32_t max_key_len, mh_tx_header *hdrs_out, uint8_t *alh_out,
+                             int32_t *status_out, uint64_t *nbad_out, uint64_t *first_bad_out) {
+    {
         const uint32_t es = clog_entry_size;
         if (!c || (es != 12 && es != 44) || (ntx && (!dlog || !clog))) return MH_ERR_ILLEGAL_ARGUMENTS;
         if (nbad_out) *nbad_out = 0;
         if (first_bad_out) *first_bad_out = ntx;
         if (!ntx) return MH_OK;
         if (ntx > (1ull << 40)) return MH_ERR_ILLEGAL_ARGUMENTS;
-        std::lock_guard<std::mutex> lk(c->mu);
         hipSetDevice(c->device);
         MH_HIP(c->copy_lane());
         hipStream_t st = c->stream;
@@ -339,5 +338,20 @@ extern "C" int mh_txlog_validate_clog(mh_ctx *c, const uint8_t *dlog, uint64_t l
         if (nbad_out) *nbad_out = hs[2];
         if (first_bad_out) *first_bad_out = hs[2] ? hs[3] : ntx;
         return MH_OK;
+    }
+}
+
+extern "C" int mh_txlog_validate_clog(mh_ctx *c, const uint8_t *dlog, uint64_t len,
+                                      const uint8_t *clog, uint64_t ntx, uint32_t clog_entry_size,
+                                      uint32_t max_entries, uint32_t max_key_len,
+                                      mh_tx_header *hdrs_out, uint8_t *alh_out,
+                                      int32_t *status_out, uint64_t *nbad_out,
+                                      uint64_t *first_bad_out) {
+    return mh_guard([&]() -> int {
+        if (!c) return MH_ERR_ILLEGAL_ARGUMENTS;
+        std::lock_guard<std::mutex> lk(c->mu);
+        return txlog_validate_clog_core(c, dlog, len, clog, ntx, clog_entry_size, max_entries,
+                                        max_key_len, hdrs_out, alh_out, status_out, nbad_out,
+                                        first_bad_out);
     });
 }

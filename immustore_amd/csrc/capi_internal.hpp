@@ -193,6 +193,8 @@ struct mh_ctx {
     DevBuf s_txlog;       // raw tx-log bytes of mh_txlog_validate
     DevBuf s_txpatch;     // the same + canonical metadata records (rare)
     DevBuf s_clog;        // mh_txlog_validate_clog's per-record arrays
+    DevBuf s_ans, s_ans_tx, s_ans_ent, s_ans_out;  // mh_verifiable_answer_pb_batch: per request,
+                                                   // per distinct tx, per entry, the bytes
     uint64_t clog_wmax = 0;  // the widest record of its last resident call (the next launch's guess)
     // mh_txlog_validate's groups (one per copy chunk): device arrays and
     // pinned index staging of each, kept across calls
@@ -360,6 +362,13 @@ std::vector<uint64_t> txlog_chunk_cuts(const uint8_t *log, uint64_t len, bool re
 int txlog_validate_core(mh_ctx *c, const uint8_t *buf, const uint8_t *dlog, uint64_t len,
                         HopLimits lim, uint64_t max_txs, uint64_t *ntx_out, uint64_t *consumed_out,
                         const TxlogOutputs &out, const HopView *parsed);
+
+// mh_txlog_validate_clog's body (capi_clog.hip), same arguments and results.
+// c->mu MUST be held by the caller.
+int txlog_validate_clog_core(mh_ctx *c, const uint8_t *dlog, uint64_t len, const uint8_t *clog,
+                             uint64_t ntx, uint32_t clog_entry_size, uint32_t max_entries,
+                             uint32_t max_key_len, mh_tx_header *hdrs_out, uint8_t *alh_out,
+                             int32_t *status_out, uint64_t *nbad_out, uint64_t *first_bad_out);
 
 // Host-to-device copies of a call cut into chunks, issued from one helper
 // thread (or two, chunk k on lane k % 2) onto the context's copy stream(s)

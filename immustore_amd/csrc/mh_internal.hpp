@@ -667,4 +667,104 @@ hipError_t launch_pb_dual_v1(hipStream_t st, Timer *tm, int phase, const uint8_t
                              const MhTxHeader *tgt, const uint8_t *md_blob, uint64_t first_tx,
                              uint64_t count, const uint8_t *alh, const uint8_t *inner, uint8_t *out,
                              uint64_t out_cap, uint64_t *off, int32_t *status, uint8_t *scratch);
+
+// ---------------------------------------------------------------- whole answers (answer_kernels.hip)
+// The txs one mh_verifiable_answer_pb_batch call reads, as a bitmap over
+// [1, ntx] (bit x - 1 of bits: tx x is read) with rank[w] = the set bits below
+// word w: tx x lies in slot rank[(x-1)/64] + popcount(bits below it) of the
+// compacted per-tx arrays.  It is the DualProof (v1) writer's digest window
+// in that call: rst[slot] is the record's verdict, lnk[slot] != 0 says that the
+// stored PrevAlh is not the Alh of the tx before it (tx_reader.go:87-89).
+struct RankWindow {
+    const uint64_t *bits, *rank;
+    const int32_t *rst;
+    const uint8_t *lnk;
+    uint64_t ntx;
+    const uint64_t *pos;  // phase 2: where message p goes in `out`
+#ifdef __HIPCC__
+    __device__ __forceinline__ bool has(uint64_t x) const {
+        return x >= 1 && x <= ntx && ((bits[(x - 1) >> 6] >> ((x - 1) & 63)) & 1);
+    }
+    __device__ __forceinline__ uint64_t slot(uint64_t x) const {  // has(x)
+        const uint64_t b = x - 1, w = bits[b >> 6];
+        return rank[b >> 6] + (uint64_t)__popcll(w & ((1ull << (b & 63)) - 1));
+    }
+    // the reads of txs lo .. hi in the reader's order: a record's verdict, then
+    // its link to the one before (lo <= hi)
+    __device__ __forceinline__ int32_t check(uint64_t lo, uint64_t hi) const {
+        if (lo < 1 || hi > ntx) return MH_ERR_TX_NOT_FOUND;
+        if (!has(lo)) return MH_ERR_ILLEGAL_STATE;
+        const uint64_t s = slot(lo);
+        for (uint64_t k = lo; k <= hi; k++) {
+            if (!has(k)) return MH_ERR_ILLEGAL_STATE;  // not in the call's read set: never seen
+            const uint64_t j = s + (k - lo);
+            if (rst[j]) return rst[j];
+            if (k > lo && lnk[j]) return MH_ERR_CORRUPTED_TX_DATA;
+        }
+        return MH_OK;
+    }
+    __device__ __forceinline__ uint64_t at(uint64_t p, const uint64_t *) const { return pos[p]; }
+#endif
+};
+hipError_t launch_pb_dual_v1_ranked(hipStream_t st, Timer *tm, int phase, const uint8_t *dlog,
+                                    uint64_t size, uint64_t n, const MhTxHeader *src,
+                                    const MhTxHeader *tgt, const uint8_t *md_blob,
+                                    const RankWindow &win, const uint8_t *alh, const uint8_t *inner,
+                                    uint8_t *out, uint64_t *off, int32_t *status, uint8_t *scratch);
+
+// Every device array of one mh_verifiable_answer_pb_batch call.  n requests,
+// D distinct txs read (slots), E entries of the asked txs.
+struct AnsArrays {
+    // the store
+    const uint8_t *txlog, *clog;
+    uint64_t txlog_len, ntx;
+    uint32_t es;
+    // requests
+    uint64_t n;
+    const uint8_t *kind;
+    const uint64_t *tx, *since;
+    const uint8_t *keys, *entries;
+    const uint64_t *key_off, *entry_off;
+    int32_t *pre;           // steps 1-4 of the status list
+    MhTxHeader *hs, *ht;    // DualProof(src, tgt)
+    uint64_t *leaf;         // ENTRY: the key's entry in its tx
+    const int32_t *dst;     // the DualProof writer's status
+    const uint64_t *dp_off; // and its message lengths
+    uint64_t *sizes, *dpos;
+    const uint64_t *off;
+    int32_t *status;
+    // the read set
+    uint64_t words;         // of bits
+    uint64_t *bits, *wcnt, *rank;
+    // slots
+    uint64_t D;
+    uint64_t *ids;
+    uint8_t *gclog;
+    MhTxHeader *hd;
+    uint8_t *alh, *inner;
+    int32_t *rst;
+    uint8_t *lnk;
+    uint32_t *flags;        // 1: asked, 2: asked by an ENTRY request
+    uint64_t *ecnt, *ncnt, *txbody;
+    const uint64_t *leaf_off, *lvl_off, *txpos;
+    uint32_t *hsz;          // framed TxHeader bytes
+    uint64_t *ent_start;    // where the record's first entry lies in the log
+    // entries
+    uint64_t E;
+    uint64_t *rec_off, *esz;
+    const uint64_t *epos;
+    uint8_t *ver;
+    uint8_t *dig, *nodes, *txbuf, *out;
+    uint64_t out_cap;
+};
+hipError_t launch_ans_heads(hipStream_t st, Timer *tm, const AnsArrays &a);
+hipError_t launch_ans_popc(hipStream_t st, Timer *tm, const AnsArrays &a);
+hipError_t launch_ans_compact(hipStream_t st, Timer *tm, const AnsArrays &a);
+hipError_t launch_ans_verdict(hipStream_t st, Timer *tm, const AnsArrays &a);   // + links, counts
+hipError_t launch_ans_trees(hipStream_t st, Timer *tm, const AnsArrays &a);     // levels of the ENTRY txs
+hipError_t launch_ans_find(hipStream_t st, Timer *tm, const AnsArrays &a);      // Tx.IndexOf + entry sizes
+hipError_t launch_ans_txsize(hipStream_t st, Timer *tm, const AnsArrays &a);
+hipError_t launch_ans_size(hipStream_t st, Timer *tm, const AnsArrays &a);
+hipError_t launch_ans_tx_write(hipStream_t st, Timer *tm, const AnsArrays &a);
+hipError_t launch_ans_assemble(hipStream_t st, Timer *tm, const AnsArrays &a);
 }  // namespace mh

@@ -36,79 +36,13 @@
 
 #include "digest_io.hpp"
 #include "mh_internal.hpp"
+#include "pb_write.hpp"
 #include "proof_walk.hpp"
 
 namespace mh {
 
-
-__device__ __forceinline__ uint32_t vlen(uint64_t v) {
-    return v ? (uint32_t)((63 - __clzll(v)) / 7 + 1) : 1u;
-}
-// int32 field value as protobuf-go encodes it (sign-extended to 64 bits)
-__device__ __forceinline__ uint64_t i32v(uint32_t x) { return (uint64_t)(int64_t)(int32_t)x; }
-
-// ------------------------------------------------------------ TxHeader
-// TxMetadata.ReadFrom (tx_metadata.go:159-195) of the stored bytes, then
-// TxMetadataToProto: truncatedTxID (attribute 0, BE64) and extra (attribute
-// 1, BE16 length + bytes); a later attribute of the same code replaces an
-// earlier one (Go map assignment).
-struct PbHdr {
-    uint32_t body = 0;      // TxHeader message length
-    uint32_t md_body = 0;   // TxMetadata message length
-    uint64_t trunc = 0;
-    uint32_t extra_off = 0, extra_len = 0;
-    bool has_md = false;
-    int32_t st = MH_OK;
-};
-
-__device__ inline PbHdr pb_header(const MhTxHeader &h, const uint8_t *md_blob) {
-    PbHdr r;
-    if (h.md_len) {  // tx.go:483-501: mdLen == 0 leaves Metadata nil
-        r.has_md = true;
-        if (h.md_len > MH_MAX_TX_METADATA_LEN) {
-            r.st = MH_ERR_CORRUPTED_DATA;
-            return r;
-        }
-        const uint8_t *b = md_blob + h.md_off;
-        uint32_t i = 0;
-        while (i < h.md_len) {
-            const uint8_t code = b[i++];
-            if (code == 0) {
-                if (h.md_len - i < 8) { r.st = MH_ERR_CORRUPTED_DATA; return r; }
-                uint64_t v = 0;
-                for (int k = 0; k < 8; k++) v = v << 8 | b[i + k];
-                r.trunc = v;
-                i += 8;
-            } else if (code == 1) {
-                if (h.md_len - i < 2) { r.st = MH_ERR_CORRUPTED_DATA; return r; }
-                const uint32_t L = (uint32_t)b[i] << 8 | b[i + 1];
-                if (h.md_len - i - 2 < L) { r.st = MH_ERR_CORRUPTED_DATA; return r; }
-                r.extra_off = h.md_off + i + 2;
-                r.extra_len = L;
-                i += 2 + L;
-            } else {
-                r.st = MH_ERR_CORRUPTED_DATA;
-                return r;
-            }
-        }
-        if (r.trunc) r.md_body += 1 + vlen(r.trunc);
-        if (r.extra_len) r.md_body += 1 + vlen(r.extra_len) + r.extra_len;
-    }
-    uint32_t s = 0;
-    if (h.id) s += 1 + vlen(h.id);
-    s += 34;                                            // prevAlh
-    if (h.ts) s += 1 + vlen((uint64_t)h.ts);
-    if (h.nentries) s += 1 + vlen(i32v(h.nentries));
-    s += 34;                                            // eH
-    if (h.bl_tx_id) s += 1 + vlen(h.bl_tx_id);
-    s += 34;                                            // blRoot
-    if (h.version) s += 1 + vlen(i32v(h.version));
-    if (r.has_md) s += 1 + vlen(r.md_body) + r.md_body;
-    r.body = s;
-    return r;
-}
-
-__device__ __forceinline__ uint32_t framed(uint32_t body) { return 1 + vlen(body) + body; }
+// vlen / i32v, PbHdr / pb_header / framed (TxHeader), ByteWriter, put_rec34,
+// put_digest, put_header and load_node are in pb_write.hpp.
 
 // ------------------------------------------------------------ DualProofV2
 // ImmuStore.DualProofV2 (immustore.go:2356-2387) checks and proof bounds.
@@ -170,152 +104,7 @@ __global__ __launch_bounds__(256) void k_pb_dual_size(const uint8_t *__restrict_
 }
 
 // ------------------------------------------------------------ byte streams
-// One lane writes one message.  Bytes collect in a 32-bit register and leave
-// as dword stores; only the partial words at the two ends of a run (shared
-// with the neighbouring messages / records) are written byte by byte.
-// global-memory pointer types: stores through them are global_* rather than
-// flat_* (a pointer rebuilt from an integer or read from LDS is generic)
-typedef __attribute__((address_space(1))) uint8_t g8;
-typedef __attribute__((address_space(1))) uint32_t g32;
-
-struct ByteWriter {
-    g32 *w;            // dword that receives the pending bytes
-    uint32_t acc = 0;  // pending bytes, little-endian
-    uint32_t fill;     // bytes already in *w's slot (pending or not ours)
-    uint32_t lo;       // first byte of the current word that is ours
-    __device__ explicit ByteWriter(uint8_t *p)
-        : w((g32 *)((g8 *)p - ((uintptr_t)p & 3))),
-          fill((uint32_t)((uintptr_t)p & 3)), lo((uint32_t)((uintptr_t)p & 3)) {}
-    __device__ __forceinline__ void flush_word() {  // fill == 4
-        if (lo == 0) {
-            *w = acc;
-        } else {
-            g8 *b = (g8 *)w;
-            for (uint32_t k = lo; k < 4; k++) b[k] = (uint8_t)(acc >> (8 * k));
-            lo = 0;
-        }
-        w++;
-        acc = 0;
-        fill = 0;
-    }
-    __device__ __forceinline__ void put8(uint32_t b) {
-        acc |= (b & 0xff) << (8 * fill);
-        if (++fill == 4) flush_word();
-    }
-    // 4 bytes, little-endian in x (a word as loaded from memory)
-    __device__ __forceinline__ void put32(uint32_t x) {
-        if (fill == 0) {
-            acc = x;
-            fill = 4;
-            flush_word();
-        } else {
-            const uint32_t sh = 8 * fill;
-            acc |= x << sh;
-            const uint32_t rest = x >> (32 - sh);
-            fill = 4;
-            flush_word();
-            acc = rest;
-            fill = sh / 8;
-        }
-    }
-    __device__ __forceinline__ void varint(uint64_t v) {
-        while (v >= 0x80) {
-            put8((uint32_t)(v | 0x80));
-            v >>= 7;
-        }
-        put8((uint32_t)v);
-    }
-    __device__ __forceinline__ void finish() {  // the trailing partial word
-        g8 *b = (g8 *)w;
-        for (uint32_t k = lo; k < fill; k++) b[k] = (uint8_t)(acc >> (8 * k));
-    }
-    __device__ __forceinline__ uint8_t *pos() const { return (uint8_t *)((g8 *)w + fill); }
-};
-
-// A 34-byte field `tag, 32, d[0..31]` (repeated-bytes term or a header
-// digest) at any alignment without divergent branches: the record is built
-// as 9 little-endian words, funnel-shifted to the destination alignment a,
-// and stored as 7-8 dwords plus predicated byte / short stores for the
-// partial words at the two ends (a = 0: -/short, 1: byte+short/short+byte,
-// 2: short/-, 3: byte/byte).
-template <int AS>  // address space of the destination: 0 generic, 1 global
-__device__ __forceinline__ void put_rec34_as(uint8_t *pg, uint32_t tag, const uint32_t d[8]) {
-    typedef __attribute__((address_space(AS))) uint8_t b8;
-    typedef __attribute__((address_space(AS))) uint16_t b16;
-    typedef __attribute__((address_space(AS))) uint32_t b32;
-    b8 *p = (b8 *)pg;
-    uint32_t r[10];
-    r[0] = (tag & 0xff) | (32u << 8) | (d[0] << 16);
-#pragma unroll
-    for (int k = 1; k < 8; k++) r[k] = (d[k - 1] >> 16) | (d[k] << 16);
-    r[8] = d[7] >> 16;
-    r[9] = 0;
-    const uint32_t a = (uint32_t)((uintptr_t)p & 3);
-    b32 *w = (b32 *)(p - a);
-    uint32_t o[10];
-    o[0] = r[0] << (8 * a);
-#pragma unroll
-    for (int j = 1; j < 10; j++)
-        o[j] = a ? __builtin_amdgcn_alignbyte(r[j], r[j - 1], 4 - a) : r[j];
-    b8 *wb = (b8 *)w;
-    // word 0: ours from byte a
-    if (a == 0) w[0] = o[0];
-    if (a & 1) wb[a] = (uint8_t)(o[0] >> (8 * a));
-    if (a == 1 || a == 2) *(b16 *)(wb + 2) = (uint16_t)(o[0] >> 16);
-#pragma unroll
-    for (int j = 1; j < 8; j++) w[j] = o[j];
-    // word 8: ours up to byte a + 34 - 32
-    if (a >= 2) w[8] = o[8];
-    if (a <= 1) *(b16 *)(wb + 32) = (uint16_t)o[8];
-    if (a == 1) wb[34] = (uint8_t)(o[8] >> 16);
-    if (a == 3) wb[36] = (uint8_t)o[9];
-}
-
-__device__ __forceinline__ void put_rec34(uint8_t *p, uint32_t tag, const uint32_t d[8]) {
-    put_rec34_as<0>(p, tag, d);
-}
-
-// 32-byte digest field (tag, length 32, bytes; d 8-byte aligned): the byte
-// stream is closed, the field stored by put_rec34 and the stream reopened.
-__device__ __forceinline__ void put_digest(ByteWriter &bw, uint32_t tag, const uint8_t *d) {
-    const uint2 *q = reinterpret_cast<const uint2 *>(d);
-    uint32_t x[8];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const uint2 v = q[k];
-        x[2 * k] = v.x;
-        x[2 * k + 1] = v.y;
-    }
-    bw.finish();
-    uint8_t *p = bw.pos();
-    put_rec34_as<1>(p, tag, x);
-    bw = ByteWriter(p + 34);
-}
-
-// TxHeader as field `tag` of the enclosing message
-__device__ inline void put_header(ByteWriter &bw, uint32_t tag, const MhTxHeader &h,
-                                  const PbHdr &r, const uint8_t *md_blob) {
-    bw.put8(tag);
-    bw.varint(r.body);
-    if (h.id) { bw.put8(0x08); bw.varint(h.id); }
-    put_digest(bw, 0x12, h.prev_alh);
-    if (h.ts) { bw.put8(0x18); bw.varint((uint64_t)h.ts); }
-    if (h.nentries) { bw.put8(0x20); bw.varint(i32v(h.nentries)); }
-    put_digest(bw, 0x2a, h.eh);
-    if (h.bl_tx_id) { bw.put8(0x30); bw.varint(h.bl_tx_id); }
-    put_digest(bw, 0x3a, h.bl_root);
-    if (h.version) { bw.put8(0x40); bw.varint(i32v(h.version)); }
-    if (r.has_md) {
-        bw.put8(0x4a);
-        bw.varint(r.md_body);
-        if (r.trunc) { bw.put8(0x08); bw.varint(r.trunc); }
-        if (r.extra_len) {
-            bw.put8(0x12);
-            bw.varint(r.extra_len);
-            for (uint32_t q = 0; q < r.extra_len; q++) bw.put8(md_blob[r.extra_off + q]);
-        }
-    }
-}
+// ByteWriter, put_rec34 / put_digest and put_header: pb_write.hpp.
 
 // ------------------------------------------------------------ staged term records
 // Each lane owns one message, but its term records leave through LDS: per
@@ -330,13 +119,6 @@ __device__ inline void put_header(ByteWriter &bw, uint32_t tag, const MhTxHeader
 #endif
 constexpr uint32_t kRpr = MH_PB_RPR;  // records per lane per round
 constexpr uint32_t kSlotBytes = (3 + kRpr * 34 + 15) / 16 * 16;  // + alignment bytes, 16-byte rows
-
-__device__ __forceinline__ void load_node(const uint8_t *node, uint32_t x[8]) {
-    const uint4 *q = reinterpret_cast<const uint4 *>(node);  // 32-byte nodes, 16-byte aligned
-    const uint4 a = q[0], b = q[1];
-    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w;
-    x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
-}
 
 // Records q = 0 .. cnt-1 of the walk `gen` (walk order) go to
 // rec_base + 34 * (cnt - 1 - q) (proof order, proof_walk.hpp).  Wave-uniform
@@ -829,12 +611,27 @@ __device__ __forceinline__ bool pb_in_window(uint64_t first, uint64_t count, uin
     return count && lo >= first && hi - first < count;
 }
 
+// Where the writer finds the Alh / innerHash of a tx.  DenseWindow: the public
+// calls' digest window (tx x at slot x - first).  RankWindow (mh_internal.hpp):
+// the compacted list of mh_verifiable_answer_pb_batch.  check(lo, hi): the
+// status of reading txs lo .. hi in order (MH_OK: every one is there);
+// slot(x): where tx x lies in alh / inner -- a run of txs that check() passed
+// lies in consecutive slots; at(p, off): where message p goes in `out`.
+struct DenseWindow {
+    uint64_t first, count;
+    __device__ __forceinline__ int32_t check(uint64_t lo, uint64_t hi) const {
+        return pb_in_window(first, count, lo, hi) ? MH_OK : MH_ERR_TX_NOT_FOUND;
+    }
+    __device__ __forceinline__ uint64_t slot(uint64_t x) const { return x - first; }
+    __device__ __forceinline__ uint64_t at(uint64_t p, const uint64_t *off) const { return off[p]; }
+};
+
 // The checks of ImmuStore.DualProof in Go's order; the first that fires is
 // the status.  src.ID == 0 is refused (the store holds no tx 0; Go would walk
 // the tree from leaf 0), as for DualProofV2.
+template <class W>
 __device__ inline PbDual1 pb_dual1(const MhTxHeader &src, const MhTxHeader &tgt,
-                                   const uint8_t *md_blob, uint64_t size, uint64_t first,
-                                   uint64_t count) {
+                                   const uint8_t *md_blob, uint64_t size, const W &win) {
     PbDual1 d;
     if (src.id == 0) { d.st = MH_ERR_ILLEGAL_ARGUMENTS; return d; }
     if (src.id > tgt.id) { d.st = MH_ERR_SOURCE_TX_NEWER; return d; }
@@ -848,18 +645,19 @@ __device__ inline PbDual1 pb_dual1(const MhTxHeader &src, const MhTxHeader &tgt,
     if (d.cons && d.bl > size) { d.st = MH_ERR_UNEXISTENT_DATA; return d; }
     d.last = d.bl > 0;
     if (d.last) {
-        if (!pb_in_window(first, count, d.bl, d.bl)) { d.st = MH_ERR_TX_NOT_FOUND; return d; }
+        if (const int32_t e = win.check(d.bl, d.bl)) { d.st = e; return d; }
         if (d.bl > size) { d.st = MH_ERR_UNEXISTENT_DATA; return d; }
     }
     d.ls = src.id > d.bl ? src.id : d.bl;  // immustore.go:2446, :2472-2475
     d.lt = tgt.id;
     if (d.ls > d.lt) { d.st = MH_ERR_SOURCE_TX_NEWER; return d; }
-    if (!pb_in_window(first, count, d.ls, d.lt)) { d.st = MH_ERR_TX_NOT_FOUND; return d; }
+    if (const int32_t e = win.check(d.ls, d.lt)) { d.st = e; return d; }
     d.a0 = src.bl_tx_id;                   // immustore.go:2452-2456, :2514-2521
     d.a1 = src.id < d.bl ? src.id : d.bl;
     if (d.a1 < d.a0) { d.st = MH_ERR_SOURCE_TX_NEWER; return d; }
     d.adv = d.a1 - d.a0 > 1;
-    if (d.adv && !pb_in_window(first, count, d.a0 + 1, d.a1)) { d.st = MH_ERR_TX_NOT_FOUND; return d; }
+    if (d.adv)
+        if (const int32_t e = win.check(d.a0 + 1, d.a1)) { d.st = e; return d; }
     d.s = pb_header(src, md_blob);
     if (d.s.st) { d.st = d.s.st; return d; }
     d.t = pb_header(tgt, md_blob);
@@ -882,11 +680,12 @@ __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
 
 // Size pass: one wave per message, 4 per block.  Reads the headers and their
 // metadata only.
+template <class W>
 __global__ __launch_bounds__(256) void k_pb_dual1_size(uint64_t size, uint64_t n,
                                                        const MhTxHeader *__restrict__ src,
                                                        const MhTxHeader *__restrict__ tgt,
                                                        const uint8_t *__restrict__ md_blob,
-                                                       uint64_t first, uint64_t count,
+                                                       const W win,
                                                        uint64_t *__restrict__ sizes,
                                                        PbDual1Parts *__restrict__ parts,
                                                        int32_t *__restrict__ status) {
@@ -894,7 +693,7 @@ __global__ __launch_bounds__(256) void k_pb_dual1_size(uint64_t size, uint64_t n
     const int lane = threadIdx.x & 63;
     if (p >= n) return;  // wave-uniform
     const MhTxHeader &S = src[p], &T = tgt[p];
-    const PbDual1 d = pb_dual1(S, T, md_blob, size, first, count);
+    const PbDual1 d = pb_dual1(S, T, md_blob, size, win);
     auto none = [](uint32_t, uint64_t) {};
     PbDual1Parts pt = {0, 0, 0, 0, 0};
     uint64_t s = 0;
@@ -974,12 +773,13 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane) {
 }
 
 // Write pass: one wave (one block) per message.
+template <class W>
 __global__ __launch_bounds__(64) void k_pb_dual1_write(const uint8_t *__restrict__ dlog,
                                                        uint64_t size, uint64_t n,
                                                        const MhTxHeader *__restrict__ src,
                                                        const MhTxHeader *__restrict__ tgt,
                                                        const uint8_t *__restrict__ md_blob,
-                                                       uint64_t first, uint64_t count,
+                                                       const W win,
                                                        const uint8_t *__restrict__ alh,
                                                        const uint8_t *__restrict__ inner,
                                                        const uint64_t *__restrict__ off,
@@ -996,7 +796,7 @@ __global__ __launch_bounds__(64) void k_pb_dual1_write(const uint8_t *__restrict
         return;
     }
     const MhTxHeader &S = src[p], &T = tgt[p];
-    const PbDual1 d = pb_dual1(S, T, md_blob, size, first, count);
+    const PbDual1 d = pb_dual1(S, T, md_blob, size, win);
     const PbDual1Parts pt = parts[p];
     const uint32_t ni = pt.ni, nc = pt.nc, nl = pt.nl;
     const uint32_t nrec = ni + nc + 1 + nl;  // inclusion | consistency | TargetBlTxAlh | last
@@ -1004,7 +804,7 @@ __global__ __launch_bounds__(64) void k_pb_dual1_write(const uint8_t *__restrict
         if (lane == 0) status[p] = MH_ERR_ILLEGAL_STATE;
         return;
     }
-    uint8_t *o = out + off[p];
+    uint8_t *o = out + win.at(p, off);
     const uint32_t hs = framed(d.s.body);
     uint8_t *rec = o + hs + framed(d.t.body);
     uint8_t *lin = rec + 34ull * nrec;
@@ -1059,26 +859,27 @@ __global__ __launch_bounds__(64) void k_pb_dual1_write(const uint8_t *__restrict
         dst = rec + 34 * r;
         if (r == ni + nc) {  // TargetBlTxAlh: always present, zeros without a BlTxID
             tag = 0x2a;
-            return d.last ? alh + 32 * (d.bl - first) : nullptr;
+            return d.last ? alh + 32 * win.slot(d.bl) : nullptr;
         }
         tag = r < ni ? 0x1a : r < ni + nc ? 0x22 : 0x32;
         return dlog + 32 * L.idx[r];
     });
     // LinearProof.terms: Alh(ls), innerHash(ls + 1 .. lt)
+    const uint64_t ls_slot = win.slot(d.ls);
     wave_run34(d.lt - d.ls + 1, lane, [&](uint64_t q, uint8_t *&dst, uint32_t &tag) {
         dst = lin_terms + 34 * q;
         tag = 0x1a;
-        return (q ? inner : alh) + 32 * (d.ls + q - first);
+        return (q ? inner : alh) + 32 * (ls_slot + q);
     });
     if (!d.adv) return;
 
     // LinearAdvanceProof.linearProofTerms: Alh(a0 + 1), innerHash(a0 + 2 .. a1)
-    const uint64_t na = d.a1 - d.a0;
+    const uint64_t na = d.a1 - d.a0, a_slot = win.slot(d.a0 + 1);
     uint8_t *adv_terms = adv + 1 + vlen(pt.adv_body);
     wave_run34(na, lane, [&](uint64_t q, uint8_t *&dst, uint32_t &tag) {
         dst = adv_terms + 34 * q;
         tag = 0x0a;
-        return (q ? inner : alh) + 32 * (d.a0 + 1 + q - first);
+        return (q ? inner : alh) + 32 * (a_slot + q);
     });
     // LinearAdvanceProof.inclusionProofs: InclusionProof(k, bl), k = a0+1 .. a1-1
     uint8_t *cur = adv_terms + 34 * na;
@@ -1135,30 +936,52 @@ uint64_t pb_dual_v1_scratch_bytes(uint64_t n) {
 }
 
 // scratch: sizes[n] (u64) | parts[n] | scan temp
-hipError_t launch_pb_dual_v1(hipStream_t st, Timer *tm, int phase, const uint8_t *dlog,
-                             uint64_t size, uint64_t n, const MhTxHeader *src,
-                             const MhTxHeader *tgt, const uint8_t *md_blob, uint64_t first_tx,
-                             uint64_t count, const uint8_t *alh, const uint8_t *inner, uint8_t *out,
-                             uint64_t out_cap, uint64_t *off, int32_t *status, uint8_t *scratch) {
+template <class W>
+static hipError_t pb_dual_v1_run(hipStream_t st, Timer *tm, int phase, const uint8_t *dlog,
+                                 uint64_t size, uint64_t n, const MhTxHeader *src,
+                                 const MhTxHeader *tgt, const uint8_t *md_blob, const W &win,
+                                 const uint8_t *alh, const uint8_t *inner, uint8_t *out,
+                                 uint64_t out_cap, uint64_t *off, int32_t *status, uint8_t *scratch) {
     if (!n) return hipMemsetAsync(off, 0, sizeof(uint64_t), st);
     uint64_t *sizes = reinterpret_cast<uint64_t *>(scratch);
     PbDual1Parts *parts = reinterpret_cast<PbDual1Parts *>(scratch + ((n * 8 + 255) & ~255ull));
     uint8_t *temp = reinterpret_cast<uint8_t *>(parts) + ((n * sizeof(PbDual1Parts) + 255) & ~255ull);
     if (phase & 1) {
         TimerScope ts(tm, "pb_dual1_size", st);
-        hipLaunchKernelGGL(k_pb_dual1_size, dim3(grid_for(n, 4)), dim3(256), 0, st, size, n, src,
-                           tgt, md_blob, first_tx, count, sizes, parts, status);
+        hipLaunchKernelGGL(k_pb_dual1_size<W>, dim3(grid_for(n, 4)), dim3(256), 0, st, size, n, src,
+                           tgt, md_blob, win, sizes, parts, status);
         if (hipError_t e = hipGetLastError()) return e;
         if (hipError_t e = pb_offsets(st, n, sizes, off, temp)) return e;
     }
     if (phase & 2) {
         TimerScope ts(tm, "pb_dual1_write", st);
-        hipLaunchKernelGGL(k_pb_dual1_write, dim3((unsigned)n), dim3(64), 0, st, dlog, size, n, src,
-                           tgt, md_blob, first_tx, count, alh, inner, off, parts, out, out_cap,
-                           status);
+        hipLaunchKernelGGL(k_pb_dual1_write<W>, dim3((unsigned)n), dim3(64), 0, st, dlog, size, n,
+                           src, tgt, md_blob, win, alh, inner, off, parts, out, out_cap, status);
         if (hipError_t e = hipGetLastError()) return e;
     }
     return hipSuccess;
+}
+
+hipError_t launch_pb_dual_v1(hipStream_t st, Timer *tm, int phase, const uint8_t *dlog,
+                             uint64_t size, uint64_t n, const MhTxHeader *src,
+                             const MhTxHeader *tgt, const uint8_t *md_blob, uint64_t first_tx,
+                             uint64_t count, const uint8_t *alh, const uint8_t *inner, uint8_t *out,
+                             uint64_t out_cap, uint64_t *off, int32_t *status, uint8_t *scratch) {
+    return pb_dual_v1_run(st, tm, phase, dlog, size, n, src, tgt, md_blob,
+                          DenseWindow{first_tx, count}, alh, inner, out, out_cap, off, status,
+                          scratch);
+}
+
+// The same writer over the compacted list of one mh_verifiable_answer_pb_batch
+// call: phase 1 leaves message p's length in off[p + 1] - off[p], phase 2
+// writes it at out + win.pos[p] (the caller has checked that it fits).
+hipError_t launch_pb_dual_v1_ranked(hipStream_t st, Timer *tm, int phase, const uint8_t *dlog,
+                                    uint64_t size, uint64_t n, const MhTxHeader *src,
+                                    const MhTxHeader *tgt, const uint8_t *md_blob,
+                                    const RankWindow &win, const uint8_t *alh, const uint8_t *inner,
+                                    uint8_t *out, uint64_t *off, int32_t *status, uint8_t *scratch) {
+    return pb_dual_v1_run(st, tm, phase, dlog, size, n, src, tgt, md_blob, win, alh, inner, out,
+                          ~0ull, off, status, scratch);
 }
 
 }  // namespace mh

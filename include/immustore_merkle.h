@@ -91,6 +91,8 @@ extern "C" {
 #define MH_ERR_TX_NOT_REACHED 34          /* a tx behind the first refused one of its batch (no Go
                                            * sentinel: ReplicateTx is never called for it) */
 
+#define MH_ERR_KEY_NOT_FOUND 35            /* store.ErrKeyNotFound from Tx.IndexOf, tx.go:361-368 */
+
 #define MH_MAX_TX_METADATA_LEN 268 /* maxTxMetadataLen tx_metadata.go:36-39 */
 #define MH_MAX_KV_METADATA_LEN 11  /* maxKVMetadataLen kv_metadata.go:41-43 */
 
@@ -1418,6 +1420,99 @@ int mh_dev_dual_proof_pb_batch(mh_ctx *ctx, int phase, const uint8_t *dlog, uint
                                const uint8_t *md_blob, uint64_t first_tx, uint64_t count,
                                const uint8_t *alh, const uint8_t *inner, uint8_t *out,
                                uint64_t out_cap, uint64_t *off, int32_t *status, void *scratch);
+
+/* ------------------------------------------------------- whole answers, generated */
+/* The server's half of the verified reads: whole schema.VerifiableTx
+ * (schema.proto:499-508) and schema.VerifiableEntry (:523-532) messages of a
+ * store whose tx log, commit log and ahtree are resident on the device, n
+ * requests in one device pass.  MH_ANS_TX is the answer of db.VerifiableTxByID
+ * with a nil EntriesSpec (pkg/database/database.go:1462-1528) and, once the
+ * write is committed, of db.VerifiableSet (:767-814), VerifiableSetReference
+ * (reference.go:118) and VerifiableZAdd (sorted_set.go:238):
+ * VerifiableTx{tx: TxToProto(tx), dualProof}.  MH_ANS_ENTRY is the answer of
+ * db.VerifiableGet (database.go:817-896): VerifiableEntry{entry, verifiableTx,
+ * inclusionProof}; the index lookup and the value read stay with the caller,
+ * who passes the marshalled schema.Entry, embedded verbatim as field 1 (an
+ * empty range omits the field), and the key as the tx stores it
+ * (EncodeKey(vKey)).  Request p yields out[off[p] .. off[p + 1]).
+ *
+ * Marshalling as protobuf-go: TxToProto / TxEntryToProto / KVMetadataToProto
+ * (database_protoconv.go:27-67) -- key, hValue (always 32 bytes), vLen as
+ * int32(vLen) (a stored length >= 2^31 is the 10-byte varint of the negative
+ * value), metadata present iff the stored mdLen > 0 (deleted, expiration.
+ * expiresAt = the stored seconds, nonIndexable); the header as the DualProof
+ * writer encodes TxHeaderToProto (eH = the rebuilt Eh, nil metadata when mdLen
+ * == 0); signature, kvEntries and zEntries never written; inclusionProof as
+ * mh_htree_inclusion_proof_pb_batch; dualProof exactly the bytes of
+ * mh_ahtree_dual_proof_pb_batch for the same (source, target) -- but the digest
+ * window is not an argument: every tx the proof reads (tgt.BlTxID, [max(src.ID,
+ * tgt.BlTxID), tgt.ID], [src.BlTxID + 1, min(src.ID, tgt.BlTxID)] when that
+ * advance proof is not nil; immustore.go:2431, :2472-2510, :2514-2562) is read
+ * from the resident log through the cLog and re-hashed, each distinct tx once
+ * per call.
+ *
+ * status[p], first match in Go's order (N = s->ntx, S = prove_since[p], T =
+ * tx[p]):
+ *   MH_ERR_ILLEGAL_STATE      S > N (database.go:772, :822, :1467);
+ *   MH_ERR_ILLEGAL_ARGUMENTS  T == 0 (ReadTx, immustore.go:2570);
+ *   MH_ERR_TX_NOT_FOUND       T > N (immustore.go:3000);
+ *   the record verdict of tx T, exactly the status mh_txlog_validate_clog gives
+ *     that cLog entry; then, S > 0, the verdict of tx S (ReadTxHeader
+ *     re-hashes, immustore.go:3062-3095; with S == 0 the root header is T's);
+ *   MH_ERR_KEY_NOT_FOUND      ENTRY: no entry of T has the key (Tx.IndexOf,
+ *     tx.go:361-368; the first equal key decides the leaf);
+ *   the statuses of mh_ahtree_dual_proof_pb_batch for (src, tgt) = (root, T)
+ *     when S <= T, else (T, root) (database.go:1506-1512), where a tx that
+ *     cannot be read gives its record verdict at the place Go reaches it (the
+ *     lowest failing tx of a range) and a tx of a range whose stored PrevAlh is
+ *     not the Alh of the tx before it MH_ERR_CORRUPTED_TX_DATA
+ *     (tx_reader.go:87-89);
+ *   MH_ERR_BUFFER_TOO_SMALL   the message ends beyond out_cap (off[] is complete
+ *     for all n all the same: off[n] sizes a retry);
+ *   MH_OK.
+ * A failed request writes no byte and leaves the other answers as they are.
+ * n == 0 is MH_OK.  MH_ERR_ILLEGAL_ARGUMENTS before any device work: a null
+ * pointer, key_off / entry_off running backwards, a kind outside the enum, a
+ * TX request with key bytes, clog_entry_size not 12 or 44, n >= 2^31, ntx >=
+ * 2^36, txlog or clog not on the ahtree's context's device or txlog's
+ * allocation not 256 bytes longer than txlog_len; and, once the read set is
+ * known, a batch that reads 2^31 or more distinct txs.  Locks: the tree's lock
+ * first, then its context's, both held for the whole call (the order of
+ * mh_replicate_tx_batch; all scratch of the call is the context's), so calls
+ * on trees of one context run one after the other; t is not changed.  A cLog
+ * entry that points outside the log is that record's status, never a fault.
+ * Cost: every distinct tx read is re-hashed once per call.  The read set is
+ * derived from the BlTxID fields the records store: as long as the
+ * binary-linking lag of src and tgt in a sound store, up to the whole store
+ * for a record that claims another BlTxID (clipped, safe, and as costly as
+ * the walk Go does for that record).  A call with out_cap = 0 runs the whole
+ * pass except the writes to learn off[n]: a caller that knows an upper bound
+ * passes it and calls again only when a status is MH_ERR_BUFFER_TOO_SMALL. */
+enum { MH_ANS_TX = 0, MH_ANS_ENTRY = 1 };
+
+typedef struct mh_answer_store { /* a resident store, all on the ahtree's context's device */
+    const uint8_t *txlog;        /* tx-log data after its appendable header; the allocation
+                                    extends >= 256 bytes past txlog + txlog_len (checked) */
+    uint64_t txlog_len;
+    const uint8_t *clog;         /* ntx commit-log entries, device memory */
+    uint64_t ntx;                /* = the committed tx id (CommittedAlh) */
+    uint32_t clog_entry_size;    /* 12 or 44 */
+    uint32_t max_entries, max_key_len;
+} mh_answer_store;
+
+typedef struct mh_answer_batch { /* host memory, pageable or pinned */
+    uint64_t n;
+    const uint8_t *kind;         /* n: MH_ANS_* */
+    const uint64_t *tx;          /* n: the tx to read (req.Tx / txhdr.Id / vTxID) */
+    const uint64_t *prove_since; /* n: ProveSinceTx */
+    const uint8_t *keys;         /* ENTRY: the key as stored in the tx (EncodeKey(vKey)) */
+    const uint64_t *key_off;     /* n + 1; TX requests own an empty range */
+    const uint8_t *entries;      /* ENTRY: the caller's marshalled schema.Entry, embedded */
+    const uint64_t *entry_off;   /* n + 1; verbatim as field 1; empty = field omitted */
+} mh_answer_batch;
+
+int mh_verifiable_answer_pb_batch(mh_ahtree *t, const mh_answer_store *s, const mh_answer_batch *b,
+                                  uint8_t *out, uint64_t out_cap, uint64_t *off, int32_t *status);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
