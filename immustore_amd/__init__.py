@@ -28,5 +28,7 @@ from . import replicate
 from .replicate import REPLICATED_ENTRY, replicate_tx_batch
 from . import answers
 from .answers import ResidentStore, verifiable_answers, VerifiableTxByID, VerifiableGet
+from . import export
+from .export import ExportStore, export_tx_batch
 
 __all__ = [n for n in dir() if not n.startswith("_")]

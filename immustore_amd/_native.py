@@ -405,6 +405,7 @@ SIGNATURES = {
                                      C.POINTER(u64), C.POINTER(u64)]),
     "mh_replicate_tx_batch": (i32, [vp, vp, vp, C.POINTER(u64), vp, u8p, u8p, vp, vp, u64, u8p]),
     "mh_verifiable_answer_pb_batch": (i32, [vp, vp, vp, u8p, u64, vp, vp]),
+    "mh_export_tx_batch": (i32, [vp, vp, u64, u64, u8p, u64, vp, vp, u8p]),
     "mh_commit_pipe_new": (i32, [vp, u64, C.POINTER(vp)]),
     "mh_commit_pipe_free": (i32, [vp]),
     "mh_precommit_batch": (i32, [vp, i32, u64, u64, vp, u8p, vp, u8p, vp, u8p, vp, u8p, u8p, u8p,

@@ -439,22 +439,6 @@ __global__ __launch_bounds__(256) void k_ans_tx_entries(const AnsArrays a) {
 }
 
 // ---------------------------------------------------------------- the answers
-// len bytes by the whole wave: 16-byte stores where the destination allows,
-// bytes at the two ends
-__device__ __forceinline__ void wave_copy(uint8_t *dst, const uint8_t *src, uint64_t len, int lane) {
-    const uint64_t head = std::min<uint64_t>(len, (16 - ((uintptr_t)dst & 15)) & 15);
-    for (uint64_t i = lane; i < head; i += 64) dst[i] = src[i];
-    const uint64_t nq = (len - head) / 16;
-    uint4 *d4 = reinterpret_cast<uint4 *>(dst + head);
-    const uint8_t *s = src + head;
-    for (uint64_t q = lane; q < nq; q += 64) {
-        uint4 v;
-        __builtin_memcpy(&v, s + 16 * q, 16);
-        d4[q] = v;
-    }
-    for (uint64_t i = head + 16 * nq + lane; i < len; i += 64) dst[i] = src[i];
-}
-
 // One wave per answer: the length prefixes on lane 0, the caller's Entry and
 // the encoded Tx copied by the wave, the inclusion terms a lane per term.
 // Leaves where the DualProof goes in dpos[p].

@@ -195,6 +195,8 @@ struct mh_ctx {
     DevBuf s_clog;        // mh_txlog_validate_clog's per-record arrays
     DevBuf s_ans, s_ans_tx, s_ans_ent, s_ans_out;  // mh_verifiable_answer_pb_batch: per request,
                                                    // per distinct tx, per entry, the bytes
+    DevBuf s_exp, s_exp_ent, s_exp_out;  // mh_export_tx_batch: per tx, per entry, the blobs of
+                                         // a call whose out is host memory
     uint64_t clog_wmax = 0;  // the widest record of its last resident call (the next launch's guess)
     // mh_txlog_validate's groups (one per copy chunk): device arrays and
     // pinned index staging of each, kept across calls

@@ -93,6 +93,11 @@ size_t sha_varlen_scratch_bytes(uint64_t n);
 hipError_t launch_sha256_csr(hipStream_t st, Timer *tm, const uint8_t *buf, const uint64_t *off,
                              uint64_t n, const uint8_t *override32, const uint8_t *use_override,
                              uint8_t *out32, uint8_t *scratch);
+// The bucketing alone, for a kernel of another file that walks messages of
+// lengths len[i] (skip[i] != 0: no block, sorted last): the order in scratch,
+// or null when the batch is too small to profit (input order).
+const uint32_t *sha_varlen_order(hipStream_t st, Timer *tm, const uint64_t *len, const uint8_t *skip,
+                                 uint64_t n, uint8_t *scratch, hipError_t *err);
 // readValueAt's integrity check (immustore.go:3235) over a batch: status[i] =
 // MH_OK iff off[i+1] - off[i] == exp_len[i] (exp_len may be null) and
 // SHA256(buf[off[i] .. off[i+1])) == expect[i], else MH_ERR_CORRUPTED_DATA.
@@ -450,6 +455,74 @@ hipError_t launch_repl_verdict(hipStream_t st, Timer *tm, uint64_t n, const int3
                                const mh_tx_header *hdr, const uint8_t *alh, const uint8_t *dlog,
                                uint64_t P, const ReplPrev &prev, int32_t *full,
                                unsigned long long *first_bad);
+
+// ---- ImmuStore.ExportTx for a run of txs (capi_export.hip, export_kernels.hip).
+// Every array device memory.  Per tx (n, or n + 1 where noted) and per entry
+// of the txs whose record verdict is MH_OK (E).
+struct ExpVlog {  // value log k + 1: data[0] is its byte first_off
+    const uint8_t *data;
+    uint64_t first_off, end_off;
+};
+enum : uint8_t { kExpAvail = 0, kExpTrunc = 1, kExpNoVlog = 2 };  // an entry's class
+constexpr uint32_t kExpNone = 0xffffffffu;  // "no entry" in early_idx / vbad
+struct ExpArrays {
+    uint64_t n, E;
+    const uint8_t *txlog, *clog;  // clog: the entry of the run's first tx
+    uint32_t es, nvlogs;
+    const ExpVlog *vlogs;
+    // per tx: the read path's results, then what the export derives
+    const MhTxHeader *hd;
+    const int32_t *rst;
+    uint64_t *ecnt, *ent_start, *leaf_off /* n + 1 */;
+    uint8_t *md;          // n x kMdSlot: TxMetadata.Bytes()
+    uint32_t *mdl;        // its length
+    uint32_t *early_idx;  // the lowest entry that fails without a hash (kExpNone: none)
+    int32_t *early_st;    // and its status
+    uint32_t *vbad;       // the lowest entry whose value digest differs (atomicMin)
+    uint8_t *trunc;       // entry 0's class is kExpTrunc
+    uint64_t *size, *off /* n + 1 */;
+    int32_t *status;
+    uint8_t *trunc_out;
+    // per entry
+    uint64_t *rec_off;
+    uint8_t *ver, *cls;
+    uint64_t *esz, *epos;  // bytes of the entry in its blob, and of the tx's entries ahead of it
+    const uint8_t **vsrc;  // an available value where it lies (null: none to hash)
+    uint64_t *vlen;        // bytes to hash: the bucketing's lengths
+    uint8_t *skip;         // no value to hash
+    uint8_t *out;
+    uint64_t out_cap;  // the caller's: a blob that ends beyond it is not written
+};
+// ecnt, ent_start and leaf_off from the records and verdicts
+hipError_t launch_exp_counts(hipStream_t st, Timer *tm, const ExpArrays &a);
+// per entry: class, size, value pointer; then per tx: the class rule, the
+// canonical metadata, the blob size, off
+hipError_t launch_exp_entries(hipStream_t st, Timer *tm, const ExpArrays &a);
+hipError_t launch_exp_sizes(hipStream_t st, Timer *tm, const ExpArrays &a);
+// everything of the blobs but the available values
+hipError_t launch_exp_frame(hipStream_t st, Timer *tm, const ExpArrays &a);
+// the values: hashed, compared, copied.  arm 'A': the hashing lane stores its
+// blocks; 'B': hash-only lanes, then a wave per value copies.  perm: the
+// bucketing's order or null
+hipError_t launch_exp_values(hipStream_t st, Timer *tm, const ExpArrays &a, const uint32_t *perm,
+                             char arm);
+hipError_t launch_exp_status(hipStream_t st, Timer *tm, const ExpArrays &a);
+
+// len bytes by the whole wave: 16-byte stores where the destination allows,
+// bytes at the two ends
+__device__ __forceinline__ void wave_copy(uint8_t *dst, const uint8_t *src, uint64_t len, int lane) {
+    const uint64_t head = min(len, (uint64_t)((16 - ((uintptr_t)dst & 15)) & 15));
+    for (uint64_t i = lane; i < head; i += 64) dst[i] = src[i];
+    const uint64_t nq = (len - head) / 16;
+    uint4 *d4 = reinterpret_cast<uint4 *>(dst + head);
+    const uint8_t *s = src + head;
+    for (uint64_t q = lane; q < nq; q += 64) {
+        uint4 v;
+        __builtin_memcpy(&v, s + 16 * q, 16);
+        d4[q] = v;
+    }
+    for (uint64_t i = head + 16 * nq + lane; i < len; i += 64) dst[i] = src[i];
+}
 
 __device__ __forceinline__ void copy32_a8(uint8_t *d, const uint8_t *s) {  // both 8-byte aligned
     const uint2 *a = (const uint2 *)s;

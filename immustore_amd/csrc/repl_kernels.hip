@@ -36,36 +36,6 @@ __device__ __forceinline__ uint64_t rp_be(const uint8_t *p, int n) {
     return v;
 }
 
-// TxMetadata.Bytes() of metadata that passed tx_md_check: each attribute once
-// (the last occurrence: ReadFrom overwrites the map entry), in code order
-__device__ uint32_t tx_md_canon(const uint8_t *md, uint32_t ml, uint8_t *out) {
-    int64_t a0 = -1, a1 = -1;
-    uint32_t el = 0;
-    for (uint32_t i = 0; i < ml;) {
-        const uint32_t code = md[i++];
-        if (code == 0) {
-            a0 = i;
-            i += 8;
-        } else {
-            el = rd_be16(md + i);
-            a1 = i + 2;
-            i += 2 + el;
-        }
-    }
-    uint32_t o = 0;
-    if (a0 >= 0) {
-        out[o++] = 0;
-        for (int k = 0; k < 8; k++) out[o++] = md[a0 + k];
-    }
-    if (a1 >= 0) {
-        out[o++] = 1;
-        out[o++] = (uint8_t)(el >> 8);
-        out[o++] = (uint8_t)el;
-        for (uint32_t k = 0; k < el; k++) out[o++] = md[a1 + k];
-    }
-    return o;
-}
-
 // One exported tx b[0 .. L) at offset boff of the caller's bytes, exactly
 // ReplicateTx's reads in its order (immustore.go:2773-2881, tx.go:166-247);
 // every length is checked against L before it is followed.  WRITE (the tx

@@ -151,6 +151,61 @@ __device__ __forceinline__ int tx_md_check(const uint8_t *md, uint32_t ml, bool 
     return MH_OK;
 }
 
+// TxMetadata.Bytes() of metadata that passed tx_md_check: each attribute once
+// (the last occurrence: ReadFrom overwrites the map entry), in code order
+__device__ inline uint32_t tx_md_canon(const uint8_t *md, uint32_t ml, uint8_t *out) {
+    int64_t a0 = -1, a1 = -1;
+    uint32_t el = 0;
+    for (uint32_t i = 0; i < ml;) {
+        const uint32_t code = md[i++];
+        if (code == 0) {
+            a0 = i;
+            i += 8;
+        } else {
+            el = rd_be16(md + i);
+            a1 = i + 2;
+            i += 2 + el;
+        }
+    }
+    uint32_t o = 0;
+    if (a0 >= 0) {
+        out[o++] = 0;
+        for (int k = 0; k < 8; k++) out[o++] = md[a0 + k];
+    }
+    if (a1 >= 0) {
+        out[o++] = 1;
+        out[o++] = (uint8_t)(el >> 8);
+        out[o++] = (uint8_t)el;
+        for (uint32_t k = 0; k < el; k++) out[o++] = md[a1 + k];
+    }
+    return o;
+}
+
+// KVMetadata.Bytes() (kv_metadata.go:207-219) of metadata that passed
+// kv_md_check: deleted, expiresAt (the last one read), nonIndexable, each once
+// in code order; out holds up to MH_MAX_KV_METADATA_LEN bytes
+__device__ inline uint32_t kv_md_canon(const uint8_t *md, uint32_t ml, uint8_t *out) {
+    bool del = false, ni = false;
+    int64_t ex = -1;
+    for (uint32_t i = 0; i < ml;) {
+        const uint32_t code = md[i++];
+        if (code == 0) del = true;
+        else if (code == 2) ni = true;
+        else {
+            ex = i;
+            i += 8;
+        }
+    }
+    uint32_t o = 0;
+    if (del) out[o++] = 0;
+    if (ex >= 0) {
+        out[o++] = 1;
+        for (int k = 0; k < 8; k++) out[o++] = md[ex + k];
+    }
+    if (ni) out[o++] = 2;
+    return o;
+}
+
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t x) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) x = max(x, (uint32_t)__shfl_xor((int)x, m, 64));

@@ -22,6 +22,7 @@
 #include "mh_internal.hpp"
 #include "sha256_cdna.hpp"
 #include "digest_io.hpp"
+#include "msg_walk.hpp"
 
 namespace mh {
 
@@ -29,10 +30,12 @@ constexpr int kNbBuckets = 1024;     // block-count classes (longer messages sha
 constexpr int kNbChunk = 256 * 16;   // entries per workgroup of the sort passes
 
 // blocks of SHA256(message of L bytes) incl. padding: (L + 9 + 63) / 64;
-// entries hashed from an override count 0 (no compression)
-__device__ __forceinline__ uint32_t nb_key(const uint64_t *off, const uint8_t *use, uint64_t i) {
+// entries hashed from an override count 0 (no compression); len, when given,
+// holds the lengths themselves and off is not read
+__device__ __forceinline__ uint32_t nb_key(const uint64_t *off, const uint8_t *use, uint64_t i,
+                                           const uint64_t *len) {
     if (use && use[i]) return 0;
-    const uint64_t nb = ((off[i + 1] >= off[i] ? off[i + 1] - off[i] : 0) + 72) >> 6;
+    const uint64_t nb = ((len ? len[i] : off[i + 1] >= off[i] ? off[i + 1] - off[i] : 0) + 72) >> 6;
     return (uint32_t)(nb < (uint64_t)kNbBuckets ? nb : (uint64_t)kNbBuckets - 1);
 }
 
@@ -41,14 +44,15 @@ __device__ __forceinline__ uint32_t nb_slot(uint32_t key) { return kNbBuckets - 
 
 __global__ __launch_bounds__(256) void k_nb_hist(const uint64_t *__restrict__ off,
                                                  const uint8_t *__restrict__ use, uint64_t n,
-                                                 uint32_t *__restrict__ hist) {
+                                                 uint32_t *__restrict__ hist,
+                                                 const uint64_t *__restrict__ len) {
     __shared__ uint32_t h[kNbBuckets];
     for (int k = threadIdx.x; k < kNbBuckets; k += 256) h[k] = 0;
     __syncthreads();
     const uint64_t e0 = (uint64_t)blockIdx.x * kNbChunk;
     for (int k = threadIdx.x; k < kNbChunk; k += 256) {
         const uint64_t i = e0 + k;
-        if (i < n) atomicAdd(&h[nb_slot(nb_key(off, use, i))], 1u);
+        if (i < n) atomicAdd(&h[nb_slot(nb_key(off, use, i, len))], 1u);
     }
     __syncthreads();
     for (int k = threadIdx.x; k < kNbBuckets; k += 256)
@@ -77,7 +81,8 @@ __global__ __launch_bounds__(kNbBuckets) void k_nb_scan(const uint32_t *__restri
 __global__ __launch_bounds__(256) void k_nb_scatter(const uint64_t *__restrict__ off,
                                                     const uint8_t *__restrict__ use, uint64_t n,
                                                     uint32_t *__restrict__ cursor,
-                                                    uint32_t *__restrict__ perm) {
+                                                    uint32_t *__restrict__ perm,
+                                                    const uint64_t *__restrict__ len) {
     __shared__ uint32_t h[kNbBuckets];
     __shared__ uint32_t base[kNbBuckets];
     for (int k = threadIdx.x; k < kNbBuckets; k += 256) h[k] = 0;
@@ -89,7 +94,7 @@ __global__ __launch_bounds__(256) void k_nb_scatter(const uint64_t *__restrict__
     for (int r = 0; r < kPer; r++) {
         const uint64_t i = e0 + threadIdx.x + r * 256;
         if (i < n) {
-            slot[r] = nb_slot(nb_key(off, use, i));
+            slot[r] = nb_slot(nb_key(off, use, i, len));
             rank[r] = atomicAdd(&h[slot[r]], 1u);
         }
     }
@@ -104,97 +109,11 @@ __global__ __launch_bounds__(256) void k_nb_scatter(const uint64_t *__restrict__
     }
 }
 
-// dword-aligned 16-byte load (gfx950 global loads need only dword alignment
-// for multi-dword widths)
-typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-
-__device__ __forceinline__ void load_window(const uint32_t *q, uint32_t d[17]) {
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        const u32x4_a4 v = *reinterpret_cast<const u32x4_a4 *>(q + 4 * c);
-        d[4 * c + 0] = v.x;
-        d[4 * c + 1] = v.y;
-        d[4 * c + 2] = v.z;
-        d[4 * c + 3] = v.w;
-    }
-    d[16] = q[16];
-}
-
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t x) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) x = max(x, (uint32_t)__shfl_xor((int)x, m, 64));
     return x;
 }
-
-// Byte mask of the first v bytes of a big-endian word (v clamped to 0..4).
-__device__ __forceinline__ uint32_t hi_mask(int v) {
-    return v >= 4 ? 0xffffffffu : (v <= 0 ? 0u : (0xffffffffu << (32 - 8 * v)));
-}
-
-__device__ __forceinline__ int clamp_rel(int64_t x) {
-    return (int)(x < -8 ? -8 : (x > 72 ? 72 : x));
-}
-
-// Per-lane view of one message in memory for the value phase: p = first byte,
-// L = length; the block builder keeps the next window prefetched.
-struct MsgWalk {
-    const uint32_t *q;      // dword holding p
-    const uint32_t *qlast;  // dword holding the last byte
-    uint32_t sel;           // v_perm selector of p's alignment
-    uint64_t L;
-    uint32_t d[17];         // window of the current block (loaded one block ahead)
-    bool pre;               // d already holds this block's window
-
-    __device__ __forceinline__ void init(const uint8_t *p, uint64_t len) {
-        const uint32_t al = (uint32_t)((uintptr_t)p & 3);
-        q = reinterpret_cast<const uint32_t *>(p - al);
-        qlast = reinterpret_cast<const uint32_t *>((uintptr_t)(p + len - 1) & ~(uintptr_t)3);
-        sel = 0x00010203u + al * 0x01010101u;
-        L = len;
-        pre = false;
-    }
-
-    // Message words of block b for the lanes with `on`.  fast (wave-uniform):
-    // every active lane has >= 2 more blocks after b, so its 68-byte window
-    // and the next one lie inside the message; the words are taken from d and
-    // the same registers then receive the next block's window, which lands
-    // under this block's compression.  Otherwise the general form (clamped
-    // loads, byte masks, 0x80, bit length in the last block nb-1).
-    __device__ __forceinline__ void block(uint32_t b, uint32_t nb, bool on, bool fast,
-                                          uint32_t w[16]) {
-        if (fast) {
-            if (!pre && on) load_window(q + 16 * (uint64_t)b, d);
-#pragma unroll
-            for (int j = 0; j < 16; j++) w[j] = __builtin_amdgcn_perm(d[j + 1], d[j], sel);
-            pre = on && b + 3 < nb;
-            if (pre) load_window(q + 16 * (uint64_t)(b + 1), d);
-            return;
-        }
-        pre = false;
-        uint32_t x[17];
-#pragma unroll
-        for (int j = 0; j < 17; j++) x[j] = 0;
-        if (on && L) {
-            const uint32_t *qb = q + 16 * (uint64_t)b;
-#pragma unroll
-            for (int j = 0; j < 17; j++) x[j] = *(qb + j <= qlast ? qb + j : qlast);
-        }
-        const int r = clamp_rel((int64_t)L - 64 * (int64_t)b);  // data bytes left at block start
-#pragma unroll
-        for (int j = 0; j < 16; j++) {
-            uint32_t y = __builtin_amdgcn_perm(x[j + 1], x[j], sel);
-            const int v = r - 4 * j;  // valid bytes in this word
-            y &= hi_mask(v);
-            if (v >= 0 && v < 4) y |= 0x80u << (24 - 8 * v);
-            w[j] = y;
-        }
-        if (b + 1 == nb) {
-            const uint64_t bits = L * 8;
-            w[14] = (uint32_t)(bits >> 32);
-            w[15] = (uint32_t)bits;
-        }
-    }
-};
 
 // One lane per message; lanes take messages in perm order (or input order
 // when perm is null).  out32[i] = SHA256(buf[off[i] .. off[i+1])), or
@@ -486,7 +405,8 @@ size_t sha_varlen_scratch_bytes(uint64_t n) {
 // is too small to profit (unsorted: 438 vs 1170 GiB/s of ragged values,
 // DESIGN.md history, round 2).
 static const uint32_t *nb_sort(hipStream_t st, Timer *tm, const uint64_t *off, const uint8_t *use,
-                               uint64_t n, uint8_t *scratch, hipError_t *err) {
+                               uint64_t n, uint8_t *scratch, hipError_t *err,
+                               const uint64_t *len = nullptr) {
     *err = hipSuccess;
     // below ~16K messages the four sort launches cost more than the divergence
     if (!scratch || n < 16384 || n >= 0xffffffffull) return nullptr;
@@ -497,11 +417,16 @@ static const uint32_t *nb_sort(hipStream_t st, Timer *tm, const uint64_t *off, c
     const unsigned chunks = (unsigned)((n + kNbChunk - 1) / kNbChunk);
     *err = hipMemsetAsync(hist, 0, kNbBuckets * sizeof(uint32_t), st);
     if (*err != hipSuccess) return nullptr;
-    hipLaunchKernelGGL(k_nb_hist, dim3(chunks), dim3(256), 0, st, off, use, n, hist);
+    hipLaunchKernelGGL(k_nb_hist, dim3(chunks), dim3(256), 0, st, off, use, n, hist, len);
     hipLaunchKernelGGL(k_nb_scan, dim3(1), dim3(kNbBuckets), 0, st, hist, cursor);
-    hipLaunchKernelGGL(k_nb_scatter, dim3(chunks), dim3(256), 0, st, off, use, n, cursor, pm);
+    hipLaunchKernelGGL(k_nb_scatter, dim3(chunks), dim3(256), 0, st, off, use, n, cursor, pm, len);
     *err = hipGetLastError();
     return pm;
+}
+
+const uint32_t *sha_varlen_order(hipStream_t st, Timer *tm, const uint64_t *len, const uint8_t *skip,
+                                 uint64_t n, uint8_t *scratch, hipError_t *err) {
+    return nb_sort(st, tm, nullptr, skip, n, scratch, err, len);
 }
 
 hipError_t launch_sha256_csr(hipStream_t st, Timer *tm, const uint8_t *buf, const uint64_t *off,

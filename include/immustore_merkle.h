@@ -1514,6 +1514,92 @@ typedef struct mh_answer_batch { /* host memory, pageable or pinned */
 int mh_verifiable_answer_pb_batch(mh_ahtree *t, const mh_answer_store *s, const mh_answer_batch *b,
                                   uint8_t *out, uint64_t out_cap, uint64_t *off, int32_t *status);
 
+/* ------------------------------------------------------------ leader path */
+/* ImmuStore.ExportTx(txID, allowPrecommitted, skipIntegrityCheck = false, tx)
+ * (immustore.go:2621-2770) for the consecutive txs first_tx .. first_tx +
+ * count - 1 of a store whose tx log, commit log and value logs are resident
+ * on ctx's device, in one device pass: readTx re-hashes every record (entry
+ * digests, hash tree, innerHash, Alh; tx.go:388-630), readValueAt reads every
+ * value from its value log and compares its SHA-256 with the entry's stored
+ * hVal (:3183-3240), and the bytes mh_replicate_tx_batch takes are written.
+ * Tx k of the run yields out[off[k] .. off[k + 1]):
+ *   BE32 len(hdr) | hdr | entries | BE16 1 | byte(truncated)
+ *   hdr = TxHeader.Bytes() (tx.go:103-164): id, PrevAlh, ts, version, then v0
+ *     BE16 nentries, v1 BE16 mdLen | TxMetadata.Bytes() | BE32 nentries, then
+ *     Eh -- the rebuilt root, the log does not store it --, BlTxID, BlRoot;
+ *   an entry = BE16 kLen | key | BE16 mdLen | KVMetadata.Bytes() | BE32 vLen |
+ *     value (the record stores the metadata ahead of the key); in a truncated
+ *     tx BE32 32 | hVal instead of vLen | value.
+ * Metadata is written as Go re-serialises it (each attribute once, in code
+ * order), whatever form the record stores.
+ * A value's place is decodeOffset(vOff) (:1429-1431): value log id = bits
+ * 56..63, offset = vOff with bits 55..62 cleared (Go's mask is 0xff << 55).
+ *   vLen == 0: nothing is read, the value is available (hVal must be
+ *     SHA256(nil));
+ *   vLen > 0, id 0: truncated (io.EOF, :3186);
+ *   vLen > 0, id in 1..nvlogs: available iff [offset, offset + vLen) lies
+ *     wholly inside [first_off, end_off) of vlogs[id - 1], else truncated
+ *     (multiapp.ReadAt's io.EOF for a missing chunk or a short read);
+ *   vLen > 0, id > nvlogs: MH_ERR_ILLEGAL_STATE (Go indexes past s.vLogs).
+ * status[k], first match:
+ *   the record verdict of the tx, exactly the status mh_txlog_validate_clog
+ *     gives that cLog entry (a cLog entry that points outside the log
+ *     included: a status, never a fault);
+ *   the status of the lowest entry that fails: MH_ERR_ILLEGAL_STATE as above;
+ *     MH_ERR_CORRUPTED_DATA for an available value whose SHA-256 is not the
+ *     stored hVal (:3235), and for an entry whose class (available /
+ *     truncated) is not entry 0's ("partially truncated transaction", :2703,
+ *     :2726; an empty value in an otherwise truncated tx is one);
+ *   MH_ERR_BUFFER_TOO_SMALL  the blob ends beyond out_cap;
+ *   MH_OK.
+ * off[] depends on the records and on what is resident, never on a hash, and
+ * is complete for all count whatever out_cap is: a call with out_cap = 0 runs
+ * the pass without the writes and leaves the size of a second call in
+ * off[count].  A tx that fails on its record, on a value log it names or on
+ * the class rule owns an empty range; one that fails on a value digest keeps
+ * its sized range with unspecified contents: the caller must not send it.
+ * The blobs of the other txs are never disturbed; no byte of out outside the
+ * written blobs is touched.  truncated[k] (nullable) is the trailer byte of an
+ * MH_OK tx, else 0.
+ * out is host memory (pageable or pinned) or memory of ctx's device (detected;
+ * then nothing is copied down); off, status, truncated are host memory.
+ * count == 0 is MH_OK with off[0] = 0.  MH_ERR_ILLEGAL_ARGUMENTS before any
+ * device work: a null ctx / s / off / status (out with out_cap > 0; txlog,
+ * clog with ntx > 0; vlogs with nvlogs > 0; data of a non-empty vLog),
+ * first_tx == 0, clog_entry_size not 12 or 44, nvlogs > 127 (MaxParallelIO),
+ * count >= 2^31, a vLog with end_off < first_off or with data not 4-byte
+ * aligned (a value's first dword is read from its aligned address), and --
+ * after the next check -- txlog, clog or a non-empty vLog's data not on ctx's
+ * device, txlog's allocation not 256 bytes longer than txlog_len, a vLog's
+ * not 256 bytes longer than end_off - first_off.  first_tx + count - 1 > ntx
+ * returns MH_ERR_TX_NOT_FOUND (immustore.go:3000).  The context's lock is
+ * held for the whole pass, so calls on one context run one after the other.
+ * No load touches a vLog outside [data, data + (end_off - first_off) + 256).
+ * Not covered: skipIntegrityCheck = true (Go then exports a zero Eh and
+ * hashes nothing); stores with EMBEDDED_VALUES.  Records with more than 1024
+ * entries or with metadata that is valid but not canonical are exported like
+ * any other: their verdict comes from the read path's host fallback, and the
+ * blob's metadata is re-serialised on the device. */
+typedef struct mh_export_vlog {  /* one value log, or the resident part of it */
+    const uint8_t *data;         /* device; data[0] is the vLog's byte first_off */
+    uint64_t first_off, end_off; /* bytes [first_off, end_off) are resident */
+} mh_export_vlog;
+
+typedef struct mh_export_store {
+    const uint8_t *txlog;        /* as mh_answer_store (256 bytes of slack, checked) */
+    uint64_t txlog_len;
+    const uint8_t *clog;         /* ntx commit-log entries, device memory */
+    uint64_t ntx;                /* committed or precommitted: the caller decides */
+    uint32_t clog_entry_size;    /* 12 or 44 */
+    uint32_t max_entries, max_key_len;
+    const mh_export_vlog *vlogs; /* host array; value log id k is vlogs[k - 1] */
+    uint32_t nvlogs;             /* <= 127 */
+} mh_export_store;
+
+int mh_export_tx_batch(mh_ctx *ctx, const mh_export_store *s, uint64_t first_tx, uint64_t count,
+                       uint8_t *out, uint64_t out_cap, uint64_t *off /* count + 1 */,
+                       int32_t *status /* count */, uint8_t *truncated /* count, nullable */);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif
