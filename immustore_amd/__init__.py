@@ -27,7 +27,7 @@ from .commit import CommitPipe, EntrySpec
 from . import replicate
 from .replicate import REPLICATED_ENTRY, replicate_tx_batch
 from . import answers
-from .answers import ResidentStore, verifiable_answers, VerifiableTxByID, VerifiableGet
+from .answers import ResidentStore, verifiable_answers, VerifiableTxByID, VerifiableGet, tx_answers, tx_list
 from . import export
 from .export import ExportStore, export_tx_batch
 

@@ -51,7 +51,10 @@ MH_ERR_TX_ALREADY_COMMITTED = 32
 MH_ERR_TX_OUT_OF_ORDER = 33
 MH_ERR_TX_NOT_REACHED = 34
 MH_ERR_KEY_NOT_FOUND = 35
+MH_ERR_EOF = 36
 MH_ANS_TX, MH_ANS_ENTRY = 0, 1
+MH_TXA_TX, MH_TXA_VERIFIABLE = 0, 1
+MH_TXA_NO_SPEC = 0xff
 
 MH_REPL_SKIP_INTEGRITY = 1
 MH_REPL_DRY_RUN = 2
@@ -211,6 +214,11 @@ class ErrKeyNotFound(MerkleError):
     """store.ErrKeyNotFound from Tx.IndexOf (tx.go:361-368)"""
 
 
+class ErrEOF(MerkleError):
+    """io.EOF from readValueAt (immustore.go:3187) or the vLog's ReadAt: the
+    value is not stored / not resident"""
+
+
 class HipError(MerkleError):
     pass
 
@@ -251,6 +259,7 @@ _ERRORS = {
     MH_ERR_TX_OUT_OF_ORDER: ErrTxOutOfOrder,
     MH_ERR_TX_NOT_REACHED: ErrTxNotReached,
     MH_ERR_KEY_NOT_FOUND: ErrKeyNotFound,
+    MH_ERR_EOF: ErrEOF,
 }
 
 vp = C.c_void_p
@@ -406,6 +415,7 @@ SIGNATURES = {
     "mh_replicate_tx_batch": (i32, [vp, vp, vp, C.POINTER(u64), vp, u8p, u8p, vp, vp, u64, u8p]),
     "mh_verifiable_answer_pb_batch": (i32, [vp, vp, vp, u8p, u64, vp, vp]),
     "mh_export_tx_batch": (i32, [vp, vp, u64, u64, u8p, u64, vp, vp, u8p]),
+    "mh_tx_answer_pb_batch": (i32, [vp, vp, vp, vp, u8p, u64, vp, vp]),
     "mh_commit_pipe_new": (i32, [vp, u64, C.POINTER(vp)]),
     "mh_commit_pipe_free": (i32, [vp]),
     "mh_precommit_batch": (i32, [vp, i32, u64, u64, vp, u8p, vp, u8p, vp, u8p, vp, u8p, u8p, u8p,

@@ -9,6 +9,10 @@ device pass.
   ImmuStore.DualProof and its tx readers  immustore.go:2394-2562, tx_reader.go:69-101
   TxToProto / TxEntryToProto              pkg/api/schema/database_protoconv.go:27-67
 
+tx_answers (mh_tx_answer_pb_batch) serves the same reads, and db.TxByID /
+db.TxScan, under an EntriesSpec: db.serializeTx (database.go:1080-1231) with
+ImmuStore.ReadValue (immustore.go:3149-3240) over an export.ExportStore.
+
 Everything runs in libimmustore_merkle.so on the tree's device; there is no
 CPU path.
 """
@@ -144,3 +148,84 @@ def VerifiableGet(store: ResidentStore, tx: int, prove_since_tx: int, key: bytes
     msgs, st, _ = verifiable_answers(store, [MH_ANS_ENTRY], [tx], [prove_since_tx], [key], [entry])
     N.check(int(st[0]))
     return msgs[0]
+
+
+# ---------------------------------------------------------------- under an EntriesSpec
+MH_TXA_TX, MH_TXA_VERIFIABLE, MH_TXA_NO_SPEC = N.MH_TXA_TX, N.MH_TXA_VERIFIABLE, N.MH_TXA_NO_SPEC
+EXCLUDE, ONLY_DIGEST, RAW_VALUE, RESOLVE = 0, 1, 2, 3  # schema.EntryTypeAction
+
+
+class _TxBatch(C.Structure):  # mh_tx_answer_batch
+    _fields_ = [("n", C.c_uint64), ("kind", C.c_void_p), ("tx", C.c_void_p),
+                ("prove_since", C.c_void_p), ("has_spec", C.c_void_p), ("kv_action", C.c_void_p),
+                ("z_action", C.c_void_p), ("sql_action", C.c_void_p), ("now_unix", C.c_int64)]
+
+
+def tx_answers_raw(store, tree, kind, tx, prove_since, specs, now_unix, out: int, out_cap: int):
+    """The C call mh_tx_answer_pb_batch as it is: out an address (host or the
+    context's device) -> (off[n + 1] uint64, status[n] int32).  store: an
+    export.ExportStore; tree: the AHtree over its Alh values on the store's
+    context, or None when no request is MH_TXA_VERIFIABLE; specs[p]: None
+    (req.EntriesSpec is nil) or (kv, z, sql), each an EntryTypeAction value or
+    None for a nil EntryTypeSpec."""
+    n = len(kind)
+    kd = np.ascontiguousarray(kind, np.uint8)
+    txa = np.ascontiguousarray(tx, np.uint64)
+    ps = np.ascontiguousarray(prove_since, np.uint64)
+    hs = np.array([sp is not None for sp in specs], np.uint8)
+    acts = np.full((3, max(n, 1)), MH_TXA_NO_SPEC, np.uint8)
+    for p, sp in enumerate(specs):
+        for k in range(3):
+            if sp is not None and sp[k] is not None:
+                acts[k, p] = sp[k]
+    b = _TxBatch()
+    b.n, b.kind, b.tx, b.prove_since, b.has_spec = n, _addr(kd), _addr(txa), _addr(ps), _addr(hs)
+    b.kv_action, b.z_action, b.sql_action = (_addr(acts[k]) for k in range(3))
+    b.now_unix = int(now_unix)
+    s = store.descriptor()
+    off = np.zeros(n + 1, np.uint64)
+    st = np.zeros(max(n, 1), np.int32)
+    N.check(N.load().mh_tx_answer_pb_batch(store.ctx.handle, tree.handle if tree is not None else None,
+                                           C.addressof(s), C.addressof(b), out, out_cap, _addr(off),
+                                           _addr(st)))
+    return off, st[:n].copy()
+
+
+def tx_answers(store, tree, kind, tx, prove_since, specs, now_unix, *, out_cap=None, size_hint=None):
+    """db.TxByID / an item of db.TxScan (kind MH_TXA_TX: the marshalled
+    schema.Tx) and db.VerifiableTxByID (MH_TXA_VERIFIABLE: the marshalled
+    schema.VerifiableTx) under an EntriesSpec (db.serializeTx,
+    pkg/database/database.go:1080-1231; ImmuStore.ReadValue, immustore.go:
+    3149-3240) -> (messages, status[n] int32, off[n + 1] uint64); the arguments
+    as tx_answers_raw's.  messages[p] is b"" for a request whose status is not
+    MH_OK.  out_cap / size_hint as verifiable_answers: with out_cap None the
+    call sizes its output itself, and a sizing pass hashes the values too."""
+    n = len(kind)
+
+    def call(cap):
+        out = np.zeros(max(cap, 1), np.uint8)
+        return (out,) + tx_answers_raw(store, tree, kind, tx, prove_since, specs, now_unix, _addr(out), cap)
+
+    if out_cap is None:
+        out, off, st = call(int(size_hint or 0))
+        if (st == N.MH_ERR_BUFFER_TOO_SMALL).any():
+            out, off, st = call(int(off[n]))
+    else:
+        out, off, st = call(out_cap)
+    msgs = [bytes(out[int(off[p]):int(off[p + 1])]) if st[p] == N.MH_OK else b"" for p in range(n)]
+    return msgs, st, off
+
+
+def tx_list(msgs) -> bytes:
+    """db.TxScan's schema.TxList of consecutive MH_TXA_TX answers: every Tx as
+    field 1 (0x0a, varint length, body)."""
+    out = bytearray()
+    for m in msgs:
+        out.append(0x0a)
+        v = len(m)
+        while v >= 0x80:
+            out.append(v & 0x7f | 0x80)
+            v >>= 7
+        out.append(v)
+        out += m
+    return bytes(out)

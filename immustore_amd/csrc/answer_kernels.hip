@@ -24,6 +24,7 @@
 
 #include "digest_io.hpp"
 #include "mh_internal.hpp"
+#include "answer_common.hpp"
 #include "pb_write.hpp"
 #include "proof_walk.hpp"
 #include "sha256_cdna.hpp"
@@ -34,12 +35,6 @@ namespace {
 
 inline unsigned grid_for(uint64_t threads, unsigned block) {
     return (unsigned)((threads + block - 1) / block);
-}
-
-__device__ __forceinline__ uint64_t be_dev(const uint8_t *p, int n) {
-    uint64_t v = 0;
-    for (int k = 0; k < n; k++) v = v << 8 | p[k];
-    return v;
 }
 
 // nodes of the flat level layout of a tree of width w (htree.go:85-110)
@@ -113,11 +108,6 @@ __global__ __launch_bounds__(256) void k_ans_heads(const AnsArrays a) {
 __global__ __launch_bounds__(256) void k_ans_popc(const AnsArrays a) {
     const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (w < a.words) a.wcnt[w] = (uint64_t)__popcll(a.bits[w]);
-}
-
-__device__ __forceinline__ uint64_t ans_slot(const AnsArrays &a, uint64_t x) {
-    const uint64_t b = x - 1, w = a.bits[b >> 6];
-    return a.rank[b >> 6] + (uint64_t)__popcll(w & ((1ull << (b & 63)) - 1));
 }
 
 // a lane per tx of the store: a tx that is read puts its id and its cLog
@@ -236,47 +226,6 @@ __global__ __launch_bounds__(64) void k_ans_trees(const AnsArrays a) {
 }
 
 // ---------------------------------------------------------------- entries
-// what TxEntryToProto makes of an entry record
-struct AnsEntry {
-    uint32_t ml, kl, vlen;
-    bool deleted = false, nonidx = false, has_exp = false;
-    uint64_t exp = 0;
-    uint32_t exp_body = 0, md_body = 0, body = 0;
-};
-
-__device__ inline AnsEntry ans_entry(const uint8_t *r) {
-    AnsEntry e;
-    e.ml = ((uint32_t)r[0] << 8) | r[1];
-    e.kl = ((uint32_t)r[2 + e.ml] << 8) | r[3 + e.ml];
-    e.vlen = (uint32_t)be_dev(r + 4 + e.ml + e.kl, 4);
-    // KVMetadata.unsafeReadFrom (kv_metadata.go:221-256); the read path took the record
-    for (uint32_t i = 0; i < e.ml;) {
-        const uint8_t code = r[2 + i++];
-        if (code == 0) {
-            e.deleted = true;
-        } else if (code == 1 && e.ml - i >= 8) {
-            e.has_exp = true;
-            e.exp = be_dev(r + 2 + i, 8);
-            i += 8;
-        } else if (code == 2) {
-            e.nonidx = true;
-        } else {
-            break;
-        }
-    }
-    if (e.ml) {
-        if (e.deleted) e.md_body += 2;
-        if (e.has_exp) {
-            e.exp_body = e.exp ? 1 + vlen(e.exp) : 0;
-            e.md_body += 2 + e.exp_body;
-        }
-        if (e.nonidx) e.md_body += 2;
-    }
-    e.body = (e.kl ? 1 + vlen(e.kl) + e.kl : 0) + 34 + (e.vlen ? 1 + vlen(i32v(e.vlen)) : 0) +
-             (e.ml ? 1 + vlen(e.md_body) + e.md_body : 0);
-    return e;
-}
-
 __global__ __launch_bounds__(256) void k_ans_esize(const AnsArrays a) {
     const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= a.E) return;
@@ -330,8 +279,6 @@ __global__ __launch_bounds__(256) void k_ans_txsize(const AnsArrays a) {
     a.hsz[j] = hsz;
     a.txbody[j] = body;
 }
-
-__device__ __forceinline__ uint64_t framed_u64(uint64_t body) { return 1 + vlen(body) + body; }
 
 // the layout of answer p (status MH_OK)
 struct AnsLayout {
@@ -402,39 +349,7 @@ __global__ __launch_bounds__(256) void k_ans_tx_entries(const AnsArrays a) {
     ByteWriter bw(a.txbuf + a.txpos[j] + a.hsz[j] + (a.epos[e] - a.epos[a.leaf_off[j]]));
     bw.put8(0x12);
     bw.varint(t.body);
-    const uint8_t *key = r + 4 + t.ml;
-    if (t.kl) {
-        bw.put8(0x0a);
-        bw.varint(t.kl);
-        for (uint32_t k = 0; k < t.kl; k++) bw.put8(key[k]);
-    }
-    {  // hValue: always 32 bytes
-        const uint8_t *hv = key + t.kl + 12;
-        uint32_t x[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++)
-            x[k] = hv[4 * k] | (uint32_t)hv[4 * k + 1] << 8 | (uint32_t)hv[4 * k + 2] << 16 |
-                   (uint32_t)hv[4 * k + 3] << 24;
-        bw.finish();
-        uint8_t *q = bw.pos();
-        put_rec34_as<1>(q, 0x12, x);
-        bw = ByteWriter(q + 34);
-    }
-    if (t.vlen) {
-        bw.put8(0x18);
-        bw.varint(i32v(t.vlen));
-    }
-    if (t.ml) {
-        bw.put8(0x22);
-        bw.varint(t.md_body);
-        if (t.deleted) { bw.put8(0x08); bw.put8(1); }
-        if (t.has_exp) {
-            bw.put8(0x12);
-            bw.put8(t.exp_body);
-            if (t.exp) { bw.put8(0x08); bw.varint(t.exp); }
-        }
-        if (t.nonidx) { bw.put8(0x18); bw.put8(1); }
-    }
+    put_entry_fields(bw, r, t);
     bw.finish();
 }
 

@@ -197,6 +197,7 @@ struct mh_ctx {
                                                    // per distinct tx, per entry, the bytes
     DevBuf s_exp, s_exp_ent, s_exp_out;  // mh_export_tx_batch: per tx, per entry, the blobs of
                                          // a call whose out is host memory
+    DevBuf s_txs;  // mh_tx_answer_pb_batch: per variant (the rest of its scratch is s_ans*)
     uint64_t clog_wmax = 0;  // the widest record of its last resident call (the next launch's guess)
     // mh_txlog_validate's groups (one per copy chunk): device arrays and
     // pinned index staging of each, kept across calls

@@ -840,4 +840,51 @@ hipError_t launch_ans_txsize(hipStream_t st, Timer *tm, const AnsArrays &a);
 hipError_t launch_ans_size(hipStream_t st, Timer *tm, const AnsArrays &a);
 hipError_t launch_ans_tx_write(hipStream_t st, Timer *tm, const AnsArrays &a);
 hipError_t launch_ans_assemble(hipStream_t st, Timer *tm, const AnsArrays &a);
+
+// ---- mh_tx_answer_pb_batch (capi_txspec.hip, txspec_kernels.hip): what the
+// call keeps beside the AnsArrays of its read set.  A variant is a distinct
+// (tx, actions) pair of the batch: its schema.Tx is laid out once.  A group is
+// a distinct (tx, classes read) pair: its values are hashed once, by the lanes
+// of its first variant (the primary).  An item is an entry of a variant's tx.
+enum : uint8_t { kTxsDrop = 0, kTxsDigest = 1, kTxsValue = 2 };  // what an item contributes
+constexpr uint8_t kTxsNoSpec = 0xff;  // a variant's mode: TxToProto; else kv | z << 2 | sql << 4
+struct TxsArrays {
+    const ExpVlog *vlogs;
+    uint32_t nvlogs;
+    int64_t now;
+    // per request
+    const uint8_t *kind;  // MH_TXA_*
+    const uint32_t *rv;   // its variant
+    int32_t *wst;         // the DualProof writer's phase 2: MH_OK where the answer is written
+    // per variant (V, or V + 1 where noted), the first six from the host
+    uint64_t V;
+    const uint64_t *vtx;
+    const uint8_t *vmode, *vprim;
+    const uint32_t *vgroup, *vfirst, *vcnt;  // its group, its first request, its requests
+    uint64_t *vslot;      // the tx's slot in the read set (~0: none)
+    uint64_t *vw, *item_off /* V + 1 */;
+    uint32_t *early_idx;  // the lowest entry that fails without a hash (kExpNone: none)
+    int32_t *early_st;
+    uint64_t *vbody;      // schema.Tx bytes (0: a header the writer cannot encode)
+    uint32_t *vhsz;       // of them the framed TxHeader
+    uint64_t *vshare, *vpos /* V + 1 */;  // bytes in txbuf (a variant of several requests), scanned
+    uint8_t **vdst;       // where its schema.Tx is written (null: nowhere)
+    uint32_t *gbad;       // per group: the lowest entry whose value digest differs (atomicMin)
+    // per item
+    uint64_t I;
+    uint8_t *ikind, *ifail;  // kTxs*; the status of an entry that fails without a hash
+    uint64_t *isz, *ipos;    // framed TxEntry bytes, and those of the variant's entries ahead
+    const uint8_t **vsrc;    // a value to write where it lies
+    uint64_t *vlen;          // bytes to hash: the bucketing's lengths (0 off the primary)
+    uint8_t *skip;
+    uint8_t *txbuf;
+};
+hipError_t launch_txs_variants(hipStream_t st, Timer *tm, const AnsArrays &a, const TxsArrays &x);
+hipError_t launch_txs_plan(hipStream_t st, Timer *tm, const AnsArrays &a, const TxsArrays &x);
+hipError_t launch_txs_size(hipStream_t st, Timer *tm, const AnsArrays &a, const TxsArrays &x);
+hipError_t launch_txs_write(hipStream_t st, Timer *tm, const AnsArrays &a, const TxsArrays &x);
+hipError_t launch_txs_values(hipStream_t st, Timer *tm, const AnsArrays &a, const TxsArrays &x,
+                             const uint32_t *perm);
+hipError_t launch_txs_assemble(hipStream_t st, Timer *tm, const AnsArrays &a, const TxsArrays &x);
+hipError_t launch_txs_status(hipStream_t st, Timer *tm, const AnsArrays &a, const TxsArrays &x);
 }  // namespace mh

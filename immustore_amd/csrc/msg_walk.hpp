@@ -1,5 +1,5 @@
 // msg_walk.hpp -- a lane's view of one message in memory for the ragged SHA-256
-// kernels (varlen_kernels.hip, export_kernels.hip): the 68-byte window of a
+// kernels (varlen_kernels.hip, export_kernels.hip, txspec_kernels.hip): the 68-byte window of a
 // block, loaded one block ahead, and the message words one v_perm_b32 per word
 // makes of it (realigned and byte-swapped); the last two blocks of a message
 // take the general form with the byte masks, the 0x80 pad and the bit length.

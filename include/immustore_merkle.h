@@ -92,6 +92,8 @@ extern "C" {
                                            * sentinel: ReplicateTx is never called for it) */
 
 #define MH_ERR_KEY_NOT_FOUND 35            /* store.ErrKeyNotFound from Tx.IndexOf, tx.go:361-368 */
+#define MH_ERR_EOF 36  /* io.EOF from readValueAt (immustore.go:3187) or the vLog's ReadAt:
+                          the value is not stored / not resident */
 
 #define MH_MAX_TX_METADATA_LEN 268 /* maxTxMetadataLen tx_metadata.go:36-39 */
 #define MH_MAX_KV_METADATA_LEN 11  /* maxKVMetadataLen kv_metadata.go:41-43 */
@@ -1599,6 +1601,117 @@ typedef struct mh_export_store {
 int mh_export_tx_batch(mh_ctx *ctx, const mh_export_store *s, uint64_t first_tx, uint64_t count,
                        uint8_t *out, uint64_t out_cap, uint64_t *off /* count + 1 */,
                        int32_t *status /* count */, uint8_t *truncated /* count, nullable */);
+
+/* ------------------------------------------- tx answers under an EntriesSpec */
+/* db.TxByID (pkg/database/database.go:1034-1063), one item of db.TxScan's
+ * TxList (:1531-1583) and db.VerifiableTxByID (:1462-1528) for n requests over
+ * a store whose tx log, commit log and value logs are resident on ctx's
+ * device, in one device pass: ReadTx re-hashes the record, db.serializeTx
+ * (:1080-1231) walks its entries under the request's EntriesSpec,
+ * ImmuStore.ReadValue (immustore.go:3149-3179) reads every asked value where
+ * it lies in its value log and readValueAt (:3183-3240) compares its SHA-256
+ * with the entry's stored hVal.  MH_TXA_TX yields the marshalled schema.Tx,
+ * MH_TXA_VERIFIABLE the marshalled schema.VerifiableTx{tx, dualProof}; request
+ * p owns out[off[p] .. off[p + 1]).  The store is mh_export_tx_batch's; t is
+ * the ahtree over the store's Alh values as for mh_verifiable_answer_pb_batch,
+ * must live on ctx and may be NULL iff no request is VERIFIABLE.
+ *
+ * has_spec[p] == 0 (req.EntriesSpec is nil, database.go:1081-1083):
+ *   TxToProto(tx): every entry with key, hValue, vLen and metadata, whatever
+ *   its key's first byte; the actions are ignored.  A VERIFIABLE request then
+ *   yields exactly the bytes of mh_verifiable_answer_pb_batch for MH_ANS_TX
+ *   with the same (tx, prove_since).
+ * has_spec[p] == 1: the header is TxHeaderToProto (eH = the rebuilt root);
+ *   the entries are walked in record order and classified by key[0]
+ *   (database.go:1092-1227): 0 (SetKeyPrefix) takes kv_action[p], 1
+ *   (SortedSetKeyPrefix) z_action[p], 2 (SQLPrefix) sql_action[p]; any other
+ *   first byte drops the entry; an empty key is MH_ERR_ILLEGAL_STATE at that
+ *   entry's place in the order (Go indexes e.Key()[0] and panics).  Per action
+ *   (schema.EntryTypeAction; MH_TXA_NO_SPEC: that EntryTypeSpec is nil):
+ *     MH_TXA_NO_SPEC, EXCLUDE (0)  dropped;
+ *     ONLY_DIGEST (1)  TxEntryToProto(e) appended to Tx.entries;
+ *     RAW_VALUE (2)    ReadValue(e), then TxEntryToProto(e) with value (field
+ *                      5) appended to Tx.entries;
+ *     RESOLVE (3)      SQL: MH_ERR_ILLEGAL_ARGUMENTS ("sql entry resolution is
+ *                      not supported", :1225), reached only when the tx has an
+ *                      SQL entry and no earlier entry failed.  kv / z: needs the
+ *                      index and is not covered: the whole call returns
+ *                      MH_ERR_ILLEGAL_ARGUMENTS before any device work.
+ * ReadValue (immustore.go:3149-3179), in this order:
+ *   metadata with an expiration and expiresAt <= now_unix (!expiresAt.After(
+ *     now), whole seconds): ErrExpiredEntry: the entry is dropped, nothing is
+ *     read, no error (database.go:1104-1106);
+ *   vLen == 0: no read and no digest check (:3162-3169 returns before
+ *     readValueAt): field 5 is omitted, the entry is written as ONLY_DIGEST
+ *     writes it -- unlike mh_export_tx_batch, whose empty values are hashed;
+ *   vLen > 0: the availability classes of mh_export_tx_batch: vLog id 0, or a
+ *     range not wholly inside [first_off, end_off) of vlogs[id - 1]:
+ *     MH_ERR_EOF; id > nvlogs: MH_ERR_ILLEGAL_STATE; else SHA-256 of the value
+ *     against the stored hVal, a mismatch is MH_ERR_CORRUPTED_DATA (:3235).
+ * The first failing entry in record order decides the tx's status: a value
+ * that is never read (excluded, digest-only, expired, behind an earlier
+ * failure in Go's order) raises nothing, and the status is the lowest failing
+ * entry's whatever order the lanes ran in.
+ * Marshalling as protobuf-go, as for mh_verifiable_answer_pb_batch; TxEntry's
+ * fields in number order, so value is the last field of its entry; Tx.entries
+ * may be empty (only the header is written); kvEntries, zEntries and the
+ * server's signature are never written.
+ *
+ * status[p], first match (N = s->ntx, S = prove_since[p], T = tx[p]):
+ *   TX:         MH_ERR_ILLEGAL_ARGUMENTS T == 0 (immustore.go:2570);
+ *               MH_ERR_TX_NOT_FOUND T > N (:3000); the record verdict of tx T;
+ *   VERIFIABLE: exactly the order of mh_verifiable_answer_pb_batch:
+ *               MH_ERR_ILLEGAL_STATE S > N first (database.go:1467), then T,
+ *               the verdicts of T and S, the DualProof statuses (ahead of the
+ *               serialization, as :1514-1522 runs them);
+ *   both:       MH_ERR_CORRUPTED_DATA for header metadata the writer cannot
+ *               encode; the serializeTx status above; MH_ERR_BUFFER_TOO_SMALL
+ *               (the answer ends beyond out_cap); MH_OK.
+ * Sizes never depend on a hash: off[] is complete for all n whatever out_cap
+ * is (out_cap = 0 sizes the output and still hashes: a digest status comes
+ * ahead of MH_ERR_BUFFER_TOO_SMALL).  A request that fails ahead of
+ * serializeTx, or whose tx has an entry that fails without a hash, owns an
+ * empty range -- also when a lower entry's digest decides its status; one
+ * that fails on a value digest alone keeps its sized range with unspecified
+ * contents.  No byte of out outside the written answers is touched.  No load
+ * leaves [data, data + (end_off - first_off) + 256) of a vLog or the tx log's
+ * slack.
+ * out is host memory (pageable or pinned) or memory of ctx's device (detected;
+ * then nothing is copied down); off and status are host memory.  n == 0 is
+ * MH_OK with off[0] = 0.  MH_ERR_ILLEGAL_ARGUMENTS before any device work: a
+ * null ctx / s / b / off / status / request array (out with out_cap > 0), a
+ * kind or an action outside its enum, a VERIFIABLE request with t == NULL, t
+ * not on ctx, n >= 2^31, ntx >= 2^36, and the store checks of
+ * mh_export_tx_batch (clog_entry_size, nvlogs, the 256 bytes of slack, the
+ * 4-byte alignment of vLog data, everything on ctx's device).  Locks: the
+ * tree's first when t is given, then the context's, both for the whole call.
+ * Cost: a tx asked by several requests is located and re-hashed once per call
+ * (a TX request also reads the record its BlTxID names, as the shared read set
+ * does for a proof); a schema.Tx is laid out once per distinct (tx, actions)
+ * and a value hashed once per distinct (tx, set of classes read), not once per
+ * request.
+ * Not covered: kv / z RESOLVE, stores with EMBEDDED_VALUES, the server's
+ * signature of the state, a mh_multi_* form. */
+enum { MH_TXA_TX = 0,          /* schema.Tx: db.TxByID (database.go:1034-1063), one item of
+                                  db.TxScan's TxList (:1531-1583) */
+       MH_TXA_VERIFIABLE = 1   /* schema.VerifiableTx: db.VerifiableTxByID (:1462-1528) */ };
+#define MH_TXA_NO_SPEC 0xff    /* that EntryTypeSpec is nil */
+
+typedef struct mh_tx_answer_batch {   /* host memory, pageable or pinned */
+    uint64_t n;
+    const uint8_t  *kind;         /* n: MH_TXA_* */
+    const uint64_t *tx;           /* n */
+    const uint64_t *prove_since;  /* n: VERIFIABLE only, else ignored */
+    const uint8_t  *has_spec;     /* n: 0 = req.EntriesSpec is nil -> TxToProto */
+    const uint8_t  *kv_action;    /* n: schema.EntryTypeAction value (0..3) or MH_TXA_NO_SPEC */
+    const uint8_t  *z_action;     /* n */
+    const uint8_t  *sql_action;   /* n */
+    int64_t now_unix;             /* time.Now().Unix() for ExpiredAt, one per batch */
+} mh_tx_answer_batch;
+
+int mh_tx_answer_pb_batch(mh_ctx *ctx, mh_ahtree *t /* may be NULL iff no request is VERIFIABLE */,
+                          const mh_export_store *s, const mh_tx_answer_batch *b,
+                          uint8_t *out, uint64_t out_cap, uint64_t *off /* n + 1 */, int32_t *status /* n */);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
