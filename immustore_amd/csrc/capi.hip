@@ -677,6 +677,10 @@ static int proof_batch_host(mh_ctx *c, hipStream_t st, uint64_t n, const uint64_
     uint8_t *base = c->s_msgs.as<uint8_t>();
     MH_HIP(hipMemcpyAsync(base + b_a, a, n * 8, hipMemcpyHostToDevice, st));
     if (b) MH_HIP(hipMemcpyAsync(base + b_b, b, n * 8, hipMemcpyHostToDevice, st));
+    // the kernels write nterms[p] terms of a good row and none of a refused one:
+    // the rest of what goes back to the caller is zero, not an earlier call's
+    // terms (nodes that a reset_size or a rebuild has since removed)
+    MH_HIP(hipMemsetAsync(base + b_t, 0, n * max_terms * 32, st));
     MH_HIP(run((const uint64_t *)(base + b_a), (const uint64_t *)(base + b_b), base + b_t,
                (uint32_t *)(base + b_n), (int32_t *)(base + b_s)));
     MH_HIP(hipMemcpyAsync(terms, base + b_t, n * max_terms * 32, hipMemcpyDeviceToHost, st));

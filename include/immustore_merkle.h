@@ -26,8 +26,11 @@
  *    different threads (the context's scratch is locked and used on its own
  *    stream only).
  *  - mh_dev_* functions take DEVICE pointers, are asynchronous on the
- *    context's stream and never allocate; all other functions take HOST
- *    pointers and return after the result is in host memory.
+ *    context's stream and allocate only to grow the context's scratch, on
+ *    first use or on a larger batch (mh_dev_sha256_batch,
+ *    mh_dev_htree_build_entries*, the mh_dev_ahtree_* appends; the growth is
+ *    made under the context's lock); all other functions take HOST pointers
+ *    and return after the result is in host memory.
  */
 #ifndef IMMUSTORE_MERKLE_H
 #define IMMUSTORE_MERKLE_H
@@ -256,7 +259,10 @@ int mh_verify_values_batch(mh_ctx *ctx, uint64_t n, const uint8_t *vals, const u
 int mh_dev_verify_values_batch(mh_ctx *ctx, uint64_t n, const uint8_t *vals, const uint64_t *off,
                                const uint64_t *vlen, const uint8_t *hvals, int32_t *status);
 /* Device variants of the batch proof generators: every pointer is device
- * memory (levels of a tree of `width` leaves / a dLog of `size` appends). */
+ * memory (levels of a tree of `width` leaves / a dLog of `size` appends).
+ * Of `terms` they write the nterms[p] terms of a row with status[p] == MH_OK
+ * and nothing else: a refused row and the rest of a good one keep the caller's
+ * bytes.  The host variants hand those bytes back as zero. */
 int mh_dev_htree_inclusion_proof_batch(mh_ctx *ctx, const uint8_t *levels, uint64_t width,
                                        uint64_t n, const uint64_t *leaf, uint8_t *terms,
                                        uint32_t max_terms, uint32_t *nterms, int32_t *status);

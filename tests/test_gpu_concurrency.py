@@ -58,7 +58,7 @@ def test_threads_share_one_context():
         n = int(rng.integers(1, 2000))
         keys = [rng.bytes(int(rng.integers(1, 40))) for _ in range(n)]
         vals = [rng.bytes(int(rng.integers(0, 300))) for _ in range(n)]
-        st, _, _, root = O.build_entries(1, keys, [b""] * n, vals)
+        st, _, olv, root = O.build_entries(1, keys, [b""] * n, vals)
         assert st == 0
 
         def csr(items):
@@ -71,7 +71,7 @@ def test_threads_share_one_context():
         vb, vo = csr(vals)
         lv = torch.zeros(m.levels_len(n) * 32, dtype=torch.uint8, device="cuda")
         rt = torch.zeros(32, dtype=torch.uint8, device="cuda")
-        dev_cases.append((n, kb, ko, vb, vo, lv, rt, root))
+        dev_cases.append((n, kb, ko, vb, vo, lv, rt, root, olv.tobytes()))
     torch.cuda.synchronize()
 
     errors = []
@@ -110,14 +110,16 @@ def test_threads_share_one_context():
 
     def dev_worker():
         try:
-            for (n, kb, ko, vb, vo, lv, rt, root) in dev_cases:
+            for (n, kb, ko, vb, vo, lv, rt, root, olv) in dev_cases:
                 N.check(L.mh_dev_htree_build_entries(
                     ctx.handle, 1, n, C.c_void_p(kb.data_ptr()), C.c_void_p(ko.data_ptr()), None,
                     None, C.c_void_p(vb.data_ptr()), C.c_void_p(vo.data_ptr()), None, None, None,
                     C.c_void_p(lv.data_ptr()), C.c_void_p(rt.data_ptr())))
             ctx.synchronize()
-            for (n, kb, ko, vb, vo, lv, rt, root) in dev_cases[-1:]:
-                assert bytes(rt.cpu().numpy()) == root
+            # every queued build, not only the last: its root and all its levels
+            for r, (n, kb, ko, vb, vo, lv, rt, root, olv) in enumerate(dev_cases):
+                assert bytes(rt.cpu().numpy()) == root, ("queued build", r, n, "root")
+                assert lv.cpu().numpy().tobytes() == olv, ("queued build", r, n, "levels")
         except BaseException as e:  # noqa: BLE001
             errors.append(("dev", repr(e)))
 

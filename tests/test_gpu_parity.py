@@ -500,9 +500,20 @@ def test_ahtree_random_batches_vs_oracle(m, ctx, orc):
     with pytest.raises(m.ErrCannotResetToLargerSize):
         t.reset_size(total + 1)
     o2 = orc.AHtree()
-    # rebuild oracle to the same prefix then the same suffix
+    # an oracle fed the same prefix and then the same suffix
     t.append_batch(np.zeros((10, 32), np.uint8))
     assert t.root_at(total - 10) == o.root_at(total - 10)[1]
+    o3 = orc.AHtree(total)
+    rng3 = np.random.default_rng(21)   # the payloads of the batches above, again
+    pre = np.concatenate([rng3.integers(0, 256, (bs, 32), dtype=np.uint8)
+                          for bs in [1, 1, 2, 3, 7, 64, 1, 1000, 4096, 5, 33333, 1, 2]])
+    o3.append_batch(pre[:total - 10])
+    assert o3.dlog_bytes() == o.dlog_bytes()[:len(o3.dlog_bytes())]
+    o3.append_batch(np.zeros((10, 32), np.uint8))
+    assert t.size() == total == o3.size
+    assert t.dlog() == o3.dlog_bytes()
+    assert t.root() == (total, o3.root_at(total)[1])
+    assert t.root() != (total, o.root_at(total)[1])   # not the tree from before the reset
     # variable-size payloads (generic leaf path)
     t3 = m.AHtree(ctx)
     for ln in [0, 1, 31, 32, 33, 55, 56, 63, 64, 100, 1000]:
