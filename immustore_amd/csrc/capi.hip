@@ -324,7 +324,7 @@ extern "C" int mh_dev_htree_build_digests(mh_ctx *c, const uint8_t *digests, uin
     return mh_guard([&]() -> int {
         if (!c || (n && (!digests || !levels))) return MH_ERR_ILLEGAL_ARGUMENTS;
         MH_HIP(hipSetDevice(c->device));
-        if (((uintptr_t)digests & 15) || ((uintptr_t)levels & 15)) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (((uintptr_t)digests | (uintptr_t)levels | (uintptr_t)root) & 15) return MH_ERR_ILLEGAL_ARGUMENTS;
         LevelGeom g;
         g.init(n);
         bool rk = false;
@@ -344,7 +344,7 @@ extern "C" int mh_dev_htree_build_entries_fixed(mh_ctx *c, int version, uint64_t
         if (!c || (version != 0 && version != 1)) return MH_ERR_ILLEGAL_ARGUMENTS;
         MH_HIP(hipSetDevice(c->device));
         if (n && (!levels || (!keys && key_len) || (!vals && val_len))) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (((uintptr_t)levels & 15) || ((uintptr_t)hvals_out & 15)) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (((uintptr_t)levels | (uintptr_t)hvals_out | (uintptr_t)root) & 15) return MH_ERR_ILLEGAL_ARGUMENTS;
         LevelGeom g;
         g.init(n);
         bool rk = false;
@@ -380,6 +380,8 @@ extern "C" int mh_dev_htree_build_entries(mh_ctx *c, int version, uint64_t n, co
         MH_HIP(hipSetDevice(c->device));
         if (n && (!levels || !key_off || !val_off)) return MH_ERR_ILLEGAL_ARGUMENTS;
         if ((hval_override == nullptr) != (use_override == nullptr)) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (((uintptr_t)levels | (uintptr_t)hvals_out | (uintptr_t)hval_override | (uintptr_t)root) & 15)
+            return MH_ERR_ILLEGAL_ARGUMENTS;
         LevelGeom g;
         g.init(n);
         if (n) {
@@ -406,7 +408,7 @@ extern "C" int mh_dev_htree_reduce_nodes(mh_ctx *c, const uint8_t *nodes, uint64
     return mh_guard([&]() -> int {
         if (!c || (w && (!nodes || !levels))) return MH_ERR_ILLEGAL_ARGUMENTS;
         MH_HIP(hipSetDevice(c->device));
-        if (((uintptr_t)nodes & 15) || ((uintptr_t)levels & 15)) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (((uintptr_t)nodes | (uintptr_t)levels | (uintptr_t)root) & 15) return MH_ERR_ILLEGAL_ARGUMENTS;
         if (w >= 1 && w <= kSmallTreeMax) {  // one launch (every multi-GPU step)
             MH_HIP(launch_reduce_small(c->stream, nodes, w, levels, root));
             return MH_OK;
@@ -425,6 +427,7 @@ extern "C" int mh_dev_sha256_batch(mh_ctx *c, const uint8_t *buf, const uint64_t
                                    uint8_t *out) {
     return mh_guard([&]() -> int {
         if (!c || (n && (!off || !out))) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if ((uintptr_t)out & 15) return MH_ERR_ILLEGAL_ARGUMENTS;  // store_digest: uint4 stores
         MH_HIP(hipSetDevice(c->device));
         std::lock_guard<std::mutex> lk(c->mu);
         MH_HIP(c->s_sort.ensure(sha_varlen_scratch_bytes(n)));
@@ -721,6 +724,8 @@ extern "C" int mh_dev_htree_inclusion_proof_batch(mh_ctx *c, const uint8_t *leve
     return mh_guard([&]() -> int {
         if (!c || (n && (!levels || !leaf || !terms || !nterms || !status || !max_terms)))
             return MH_ERR_ILLEGAL_ARGUMENTS;
+        // terms are copied with uint4 loads and stores
+        if (((uintptr_t)levels | (uintptr_t)terms) & 15) return MH_ERR_ILLEGAL_ARGUMENTS;
         if (!n) return MH_OK;
         hipSetDevice(c->device);
         MH_HIP(launch_htree_proof(c->stream, c->tm(), levels, width, n, leaf, terms, max_terms, nterms,
@@ -757,6 +762,9 @@ extern "C" int mh_dev_htree_verify_inclusion_batch(mh_ctx *c, uint64_t np, const
                                                    const uint8_t *roots, uint8_t *ok) {
     return mh_guard([&]() -> int {
         if (!c || (np && (!leaf || !width || !term_off || !digests || !roots || !ok)))
+            return MH_ERR_ILLEGAL_ARGUMENTS;
+        // digests are read with uint4 loads
+        if (((uintptr_t)terms | (uintptr_t)digests | (uintptr_t)roots) & 15)
             return MH_ERR_ILLEGAL_ARGUMENTS;
         MH_HIP(hipSetDevice(c->device));
         if (!np) return MH_OK;
@@ -814,6 +822,9 @@ extern "C" int mh_dev_ahtree_verify_batch(mh_ctx *c, int kind, uint64_t np, cons
         if (!c || kind < 0 || kind > 2) return MH_ERR_ILLEGAL_ARGUMENTS;
         MH_HIP(hipSetDevice(c->device));
         if (np && (!i || !j || !term_off || !a || !b || !ok)) return MH_ERR_ILLEGAL_ARGUMENTS;
+        // digests are read and eval_out written with uint4 accesses
+        if (((uintptr_t)terms | (uintptr_t)a | (uintptr_t)b | (uintptr_t)eval_out) & 15)
+            return MH_ERR_ILLEGAL_ARGUMENTS;
         if (!np) return MH_OK;
         MH_HIP(launch_ahtree_verify(c->stream, c->tm(), kind, np, i, j, term_off, terms, a, b, ok,
                                     eval_out));
@@ -871,7 +882,7 @@ extern "C" int mh_dev_ahtree_append_batch(mh_ctx *c, uint8_t *dlog, uint64_t n0,
                                           uint8_t *roots_out) {
     return mh_guard([&]() -> int {
         if (!c || (m && (!dlog || (!payloads && plen)))) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if ((uintptr_t)dlog & 15) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (((uintptr_t)dlog | (uintptr_t)roots_out) & 15) return MH_ERR_ILLEGAL_ARGUMENTS;
         if (!m) return MH_OK;
         hipSetDevice(c->device);
         // the work-queue counter is ctx scratch: reset + launch are enqueued
@@ -914,7 +925,7 @@ extern "C" int mh_dev_ahtree_append_batch_logs(mh_ctx *c, uint8_t *dlog, uint64_
                                                uint8_t *roots_out) {
     return mh_guard([&]() -> int {
         if (!c || (m && !dlog) || !logs_ok(payloads, m, plen, p_off0)) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if ((uintptr_t)dlog & 15) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (((uintptr_t)dlog | (uintptr_t)roots_out) & 15) return MH_ERR_ILLEGAL_ARGUMENTS;
         if (!m) return MH_OK;
         hipSetDevice(c->device);
         AhtLogs lg;
@@ -939,7 +950,8 @@ extern "C" int mh_dev_ahtree_append_range(mh_ctx *c, uint8_t *dlog_range, uint64
     return mh_guard([&]() -> int {
         if (!c || (m && (!dlog_range || (!payloads && plen))) || (n0 && !peaks))
             return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (((uintptr_t)dlog_range & 15) || m > ~0ull - n0) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if ((((uintptr_t)dlog_range | (uintptr_t)roots_out) & 15) || m > ~0ull - n0)
+            return MH_ERR_ILLEGAL_ARGUMENTS;
         if (!m) return MH_OK;
         hipSetDevice(c->device);
         AhtSlots slots;
@@ -1001,6 +1013,7 @@ extern "C" int mh_dev_ahtree_put_shard_roots(mh_ctx *c, uint8_t *dlog, int shard
     return mh_guard([&]() -> int {
         if (!c || shard_bits < 0 || shard_bits > 62 || (count && (!dlog || !roots)))
             return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (((uintptr_t)dlog | (uintptr_t)roots) & 15) return MH_ERR_ILLEGAL_ARGUMENTS;
         if (!count) return MH_OK;
         hipSetDevice(c->device);
         MH_HIP(launch_ahtree_put_shard_roots(c->stream, c->tm(), dlog, shard_bits, count, roots));
@@ -1012,7 +1025,7 @@ extern "C" int mh_dev_ahtree_append_spine(mh_ctx *c, uint8_t *dlog, uint64_t n0,
                                           uint8_t *roots_out) {
     return mh_guard([&]() -> int {
         if (!c || (m && !dlog)) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if ((uintptr_t)dlog & 15) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (((uintptr_t)dlog | (uintptr_t)roots_out) & 15) return MH_ERR_ILLEGAL_ARGUMENTS;
         if (!m) return MH_OK;
         hipSetDevice(c->device);
         std::lock_guard<std::mutex> lk(c->mu);
@@ -1303,6 +1316,8 @@ extern "C" int mh_dev_ahtree_proof_batch(mh_ctx *c, int kind, const uint8_t *dlo
         if (!c || (kind != MH_AHT_INCLUSION && kind != MH_AHT_CONSISTENCY) ||
             (n && (!dlog || !i || !j || !terms || !nterms || !status || !max_terms)))
             return MH_ERR_ILLEGAL_ARGUMENTS;
+        // terms are copied with uint4 loads and stores
+        if (((uintptr_t)dlog | (uintptr_t)terms) & 15) return MH_ERR_ILLEGAL_ARGUMENTS;
         if (!n) return MH_OK;
         hipSetDevice(c->device);
         MH_HIP(launch_ahtree_proof(c->stream, c->tm(), kind, dlog, size, n, i, j, terms, max_terms,

@@ -106,6 +106,8 @@ extern "C" int mh_dev_tx_alh_batch(mh_ctx *c, uint64_t n, const mh_tx_header *hd
                                    uint8_t *inner_out, uint8_t *alh_out) {
     return mh_guard([&]() -> int {
         if (!c || (n && (!hdrs || !scratch || !alh_out))) return MH_ERR_ILLEGAL_ARGUMENTS;
+        // store_digest: uint4 stores (eh, md_blob and scratch are read and written byte by byte)
+        if (((uintptr_t)inner_out | (uintptr_t)alh_out) & 15) return MH_ERR_ILLEGAL_ARGUMENTS;
         if (!n) return MH_OK;
         hipSetDevice(c->device);
         MH_HIP(launch_tx_alh(c->stream, c->tm(), n, hdrs, md_blob, eh, scratch, nullptr, nullptr,

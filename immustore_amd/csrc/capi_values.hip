@@ -15,6 +15,7 @@ extern "C" int mh_dev_verify_values_batch(mh_ctx *c, uint64_t n, const uint8_t *
                                           const uint8_t *hvals, int32_t *status) {
     return mh_guard([&]() -> int {
         if (!c || (n && (!off || !hvals || !status))) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if ((uintptr_t)hvals & 15) return MH_ERR_ILLEGAL_ARGUMENTS;  // load_digest: uint4 loads
         if (!n) return MH_OK;
         MH_HIP(hipSetDevice(c->device));
         std::lock_guard<std::mutex> lk(c->mu);

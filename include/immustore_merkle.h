@@ -219,16 +219,31 @@ int mh_htree_verify_inclusion_batch(mh_ctx *ctx, uint64_t nproofs, const uint64_
                                     const uint8_t *roots, uint8_t *ok);
 
 /* ------------------------------------------------- htree, device-resident */
-/* BuildWith over device digests. levels: mh_htree_levels_len(n)*32 bytes. */
+/* Alignment of device digest arrays.  The kernels move a 32-byte digest as two
+ * 16-byte vector accesses, so every device array of digests named below as
+ * "16-byte aligned" must start on a 16-byte boundary; a call given a lesser
+ * pointer returns MH_ERR_ILLEGAL_ARGUMENTS before anything is launched or
+ * written.  Arrays of other types need the alignment of their element type
+ * (uint64_t offsets 8, uint32_t / int32_t 4); byte arrays (message and value
+ * bytes, keys, metadata, ok flags, protobuf output) take any alignment unless
+ * a call says otherwise.  A call writes only the bytes its contract names:
+ * an output of n rows is written inside its n rows and nowhere else. */
+/* BuildWith over device digests. levels: mh_htree_levels_len(n)*32 bytes.
+ * digests and levels 16-byte aligned; root (32 bytes, may be NULL) 16-byte
+ * aligned as well: the kernels that finish a tree store it as a digest. */
 int mh_dev_htree_build_digests(mh_ctx *ctx, const uint8_t *digests, uint64_t n, uint8_t *levels,
                                uint8_t *root);
 /* Fused value hash + entry digest + leaf + all levels for fixed-stride
  * entries without KV metadata (BASELINE configs C1/C2/C4): key i at
- * keys + i*key_len, value i at vals + i*val_len. */
+ * keys + i*key_len, value i at vals + i*val_len.  keys / vals: any alignment
+ * (a 16-byte aligned vals with val_len % 16 == 0 takes the fast loads).
+ * hvals_out (n*32, may be NULL), levels and root: 16-byte aligned. */
 int mh_dev_htree_build_entries_fixed(mh_ctx *ctx, int version, uint64_t n, const uint8_t *keys,
                                      uint32_t key_len, const uint8_t *vals, uint32_t val_len,
                                      uint8_t *hvals_out, uint8_t *levels, uint8_t *root);
-/* General CSR variant (device arrays); scratch is allocated by the context. */
+/* General CSR variant (device arrays); scratch is allocated by the context.
+ * keys / md / vals / use_override: any alignment.  hval_override, hvals_out,
+ * levels and root: 16-byte aligned. */
 int mh_dev_htree_build_entries(mh_ctx *ctx, int version, uint64_t n, const uint8_t *keys,
                                const uint64_t *key_off, const uint8_t *md, const uint64_t *md_off,
                                const uint8_t *vals, const uint64_t *val_off,
@@ -236,10 +251,12 @@ int mh_dev_htree_build_entries(mh_ctx *ctx, int version, uint64_t n, const uint8
                                uint8_t *hvals_out, uint8_t *levels, uint8_t *root);
 /* Reduce w given nodes (e.g. all-gathered per-GPU subtree roots) to a root
  * with htree's pairing rule; nodes are copied to level 0 of `levels`
- * (mh_htree_levels_len(w)*32 bytes) without leaf hashing. */
+ * (mh_htree_levels_len(w)*32 bytes) without leaf hashing.  nodes, levels and
+ * root: 16-byte aligned. */
 int mh_dev_htree_reduce_nodes(mh_ctx *ctx, const uint8_t *nodes, uint64_t w, uint8_t *levels,
                               uint8_t *root);
-/* SHA-256 of n byte ranges buf[off[i], off[i+1]) -> out (n*32). */
+/* SHA-256 of n byte ranges buf[off[i], off[i+1]) -> out (n*32).  buf: any
+ * alignment; out: 16-byte aligned. */
 int mh_dev_sha256_batch(mh_ctx *ctx, const uint8_t *buf, const uint64_t *off, uint64_t n,
                         uint8_t *out);
 /* The read-side value integrity check of ImmuStore.readValueAt
@@ -252,7 +269,8 @@ int mh_dev_sha256_batch(mh_ctx *ctx, const uint8_t *buf, const uint64_t *off, ui
  * checked).  Host variant: host memory in and out, synchronous; the value
  * bytes go up in ~64 MiB chunks on a copy stream while the previous chunk is
  * checked; *ncorrupted (may be NULL) = entries not MH_OK.  Device variant:
- * every pointer device memory, asynchronous on the context stream. */
+ * every pointer device memory, asynchronous on the context stream; vals any
+ * alignment, hvals 16-byte aligned; status[0..n) is written and nothing else. */
 int mh_verify_values_batch(mh_ctx *ctx, uint64_t n, const uint8_t *vals, const uint64_t *off,
                            const uint64_t *vlen, const uint8_t *hvals, int32_t *status,
                            uint64_t *ncorrupted);
@@ -262,7 +280,11 @@ int mh_dev_verify_values_batch(mh_ctx *ctx, uint64_t n, const uint8_t *vals, con
  * memory (levels of a tree of `width` leaves / a dLog of `size` appends).
  * Of `terms` they write the nterms[p] terms of a row with status[p] == MH_OK
  * and nothing else: a refused row and the rest of a good one keep the caller's
- * bytes.  The host variants hand those bytes back as zero. */
+ * bytes.  The host variants hand those bytes back as zero.  nterms[p] and
+ * status[p] are written for every row (nterms[p] = the proof's length even
+ * when it exceeds max_terms, 0 for a row refused for its arguments).
+ * levels / dlog and terms: 16-byte aligned.  The verifier's terms, digests and
+ * roots: 16-byte aligned; ok: n bytes, any alignment. */
 int mh_dev_htree_inclusion_proof_batch(mh_ctx *ctx, const uint8_t *levels, uint64_t width,
                                        uint64_t n, const uint64_t *leaf, uint8_t *terms,
                                        uint32_t max_terms, uint32_t *nterms, int32_t *status);
@@ -321,14 +343,17 @@ int mh_ahtree_reset_size(mh_ahtree *t, uint64_t new_size);
 int mh_ahtree_dlog(mh_ahtree *t, uint64_t first, uint64_t count, uint8_t *out);
 int mh_ahtree_dlog_device(mh_ahtree *t, const uint8_t **dptr);
 
-/* Device-resident batch append: dlog holds nodesUpto(n0) digests and has
- * room for nodesUpto(n0+m); payloads m*plen bytes. */
+/* Device-resident batch append: dlog (16-byte aligned) holds nodesUpto(n0)
+ * digests and has room for nodesUpto(n0+m); payloads m*plen bytes, any
+ * alignment.  The call writes the nodes [nodesUpto(n0), nodesUpto(n0+m)) and
+ * the m rows of roots_out (16-byte aligned, may be NULL); the nodes below
+ * nodesUpto(n0) stay as they are. */
 int mh_dev_ahtree_append_batch(mh_ctx *ctx, uint8_t *dlog, uint64_t n0, const uint8_t *payloads,
                                uint64_t m, uint32_t plen, uint8_t *roots_out);
 /* Device variants of the appendable records: fused into the append's leaf
  * phase (the payload is read once), or alone (e.g. per rank of a sharded
  * append: rank r passes p_off0 + r*S*(4+plen)).  plog / clog: device memory
- * of m*(4+plen) / m*12 bytes, either may be NULL. */
+ * of m*(4+plen) / m*12 bytes, any alignment, either may be NULL. */
 int mh_dev_ahtree_append_batch_logs(mh_ctx *ctx, uint8_t *dlog, uint64_t n0,
                                     const uint8_t *payloads, uint64_t m, uint32_t plen,
                                     uint64_t p_off0, uint8_t *plog, uint8_t *clog,
@@ -378,7 +403,10 @@ uint64_t mh_ahtree_node_index(uint64_t n, int level);
  *     global end, roots in shard order, for a batch starting at n0 = 0) writes
  *     them and the perfect nodes above them; mh_dev_ahtree_append_spine then
  *     finishes the rank's appends.  The rank's dLog range is byte-identical to
- *     a single-device append of the whole batch. */
+ *     a single-device append of the whole batch.
+ * dlog, roots and roots_out (m x 32, may be NULL): 16-byte aligned.  Of dlog
+ * the three calls write nodes of the rank's own range and the nodes above
+ * shard level, each with the value the whole batch gives it, and no other. */
 int mh_dev_ahtree_append_local(mh_ctx *ctx, uint8_t *dlog, uint64_t n0, const uint8_t *payloads,
                                uint64_t m, uint32_t plen, int shard_bits);
 int mh_dev_ahtree_put_shard_roots(mh_ctx *ctx, uint8_t *dlog, int shard_bits, uint64_t count,
@@ -391,8 +419,8 @@ int mh_dev_ahtree_append_spine(mh_ctx *ctx, uint8_t *dlog, uint64_t n0, uint64_t
  * append m payloads onto a tree of size n0 whose peaks (as for
  * mh_multi_ahtree_append_batch, host memory, NULL when n0 == 0) are given;
  * dlog_range (device, 16-byte aligned) receives the new digests
- * [nodesUpto(n0), nodesUpto(n0 + m)) from its start, roots_out (may be NULL)
- * RootAt after each append.  Asynchronous on the context stream. */
+ * [nodesUpto(n0), nodesUpto(n0 + m)) from its start, roots_out (16-byte
+ * aligned, may be NULL) RootAt after each append.  Asynchronous on the context stream. */
 int mh_dev_ahtree_append_range(mh_ctx *ctx, uint8_t *dlog_range, uint64_t n0,
                                const uint8_t *peaks, const uint8_t *payloads, uint64_t m,
                                uint32_t plen, uint8_t *roots_out);
@@ -411,7 +439,9 @@ int mh_dev_ahtree_peaks(mh_ctx *ctx, const uint8_t *dlog, uint64_t n, uint8_t *p
  * no terms (verification.go:22-24, :59-61), and for CONSISTENCY also i == j
  * with no terms (:63-65, where Go's Eval would index an empty proof) --
  * eval_out[p] is the leaf a[p] unchanged for INCLUSION and 64 zero bytes for
- * CONSISTENCY.  LAST_INCLUSION always walks, i == 0 included (ok[p] = 0). */
+ * CONSISTENCY.  LAST_INCLUSION always walks, i == 0 included (ok[p] = 0).
+ * Device variant: terms, a, b and eval_out 16-byte aligned; ok: nproofs bytes,
+ * any alignment. */
 int mh_ahtree_verify_batch(mh_ctx *ctx, int kind, uint64_t nproofs, const uint64_t *i,
                            const uint64_t *j, const uint64_t *term_off, const uint8_t *terms,
                            const uint8_t *a, const uint8_t *b, uint8_t *ok, uint8_t *eval_out);
@@ -434,7 +464,9 @@ int mh_tx_alh_batch(mh_ctx *ctx, uint64_t n, const mh_tx_header *hdrs, const uin
                     uint64_t md_blob_len, uint8_t *inner_out, uint8_t *alh_out);
 /* Device variant: hdrs / md_blob / outputs in device memory; eh (nullable,
  * n x 32) replaces hdrs[k].eh (e.g. Eh just built on the device).  scratch:
- * n * 384 bytes of device memory.  Arguments are not validated. */
+ * n * 384 bytes of device memory.  The headers' fields are not validated.
+ * hdrs: 8-byte aligned (its struct); md_blob, eh and scratch: any alignment
+ * (byte accesses); inner_out and alh_out: 16-byte aligned. */
 int mh_dev_tx_alh_batch(mh_ctx *ctx, uint64_t n, const mh_tx_header *hdrs, const uint8_t *md_blob,
                         const uint8_t *eh, uint8_t *scratch, uint8_t *inner_out, uint8_t *alh_out);
 
@@ -608,7 +640,9 @@ int mh_dual_proof_pb_decode_batch(mh_ctx *ctx, uint64_t n, const uint8_t *msgs,
  * (Eh) and Alh and compares it with the stored one: status[k] = MH_OK or
  * MH_ERR_CORRUPTED_DATA ("ALH mismatch", tx.go:625).  Optional outputs
  * (capacity max_txs): hdrs (md_off relative to buf, eh = rebuilt Eh) and
- * alh (recomputed).  KV / tx metadata are parsed as the reader parses them
+ * alh (recomputed).  Of hdrs, alh and status the rows [0, *ntx) are written;
+ * the rows from *ntx up to the capacity keep the caller's bytes (pageable,
+ * pinned or device memory alike).  KV / tx metadata are parsed as the reader parses them
  * (KVMetadata.unsafeReadFrom kv_metadata.go:221-256, TxMetadata.ReadFrom
  * tx_metadata.go:159-193): unknown attribute codes, short payloads and an
  * extra running past the metadata stop the parse with MH_ERR_CORRUPTED_DATA;
@@ -1370,7 +1404,12 @@ int mh_ahtree_dual_proof_v2_pb_batch(mh_ahtree *t, uint64_t n, const mh_tx_heade
 /* Device variants (all pointers device memory, asynchronous, no allocation):
  * scratch = mh_pb_scratch_size(n) bytes; messages beyond out_cap get status
  * MH_ERR_BUFFER_TOO_SMALL.  phase: 1 = sizes + offsets only, 2 = write only
- * (after a phase-1 call with the same inputs), 3 = both. */
+ * (after a phase-1 call with the same inputs), 3 = both.  off[0..n] and
+ * status[0..n) are written whatever out_cap is (off[n] sizes a retry); of out
+ * only the bytes [off[p], off[p+1]) of messages with status MH_OK, all below
+ * out_cap: a refused message and everything from out_cap on keep the caller's
+ * bytes.  scratch is unspecified inside its own mh_pb_scratch_size(n) bytes.
+ * out: any alignment. */
 uint64_t mh_pb_scratch_size(uint64_t n);
 int mh_dev_htree_inclusion_proof_pb_batch(mh_ctx *ctx, int phase, const uint8_t *levels,
                                           uint64_t width, uint64_t n, const uint64_t *leaf,

@@ -12,11 +12,9 @@ import numpy as np
 import pytest
 
 from ahtree_wide_util import WIDE_N0, WIDE_TOTALS, nodes_upto, sampled_rows, wide_case
+from gpu_util import FILL, GUARD, Guarded
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 4096
-FILL = 0xA5
 
 
 @pytest.fixture(scope="module")
@@ -26,27 +24,6 @@ def m():
     if m.device_count() == 0:
         pytest.fail("no GPU visible: -m gpu tests must run on the MI355X box")
     return m
-
-
-class Guarded:
-    """nbytes of device memory filled with 0xA5 between two 4096-byte guards."""
-
-    def __init__(self, nbytes):
-        import torch
-        self.n = nbytes
-        self.t = torch.full((GUARD + nbytes + GUARD,), FILL, dtype=torch.uint8, device="cuda")
-        self.ptr = self.t.data_ptr() + GUARD
-        assert self.ptr % 16 == 0
-
-    def rows(self):
-        return self.t[GUARD:GUARD + self.n].cpu().numpy().reshape(-1, 32)
-
-    def guards_intact(self):
-        return bool((self.t[:GUARD] == FILL).all().item() and
-                    (self.t[GUARD + self.n:] == FILL).all().item())
-
-    def untouched(self):
-        return bool((self.t == FILL).all().item())
 
 
 def _dev(a):
