@@ -2,17 +2,51 @@
 // VerifiableTx / VerifiableEntry answers; txspec_kernels.hip: the answers of
 // TxByID / TxScan / VerifiableTxByID under an EntriesSpec): the slot of a tx in
 // the call's read set, what TxEntryToProto makes of an entry record, and the
-// entry's fields 1 to 4 as protobuf-go lays them down.
+// entry's fields 1 to 4 as protobuf-go lays them down.  With export_kernels.hip
+// they also share the launchers' grid and launch, the owner of an item and
+// where an entry record keeps its hVal.
 #pragma once
 #include "mh_internal.hpp"
 #include "pb_write.hpp"
 
 namespace mh {
 
+inline unsigned grid_for(uint64_t threads, unsigned block) {
+    return (unsigned)((threads + block - 1) / block);
+}
+
+// One timed launch inside a launcher (st, tm in scope); an empty grid launches nothing
+#define MH_LAUNCH(name, kernel, grid, block, ...)                                 \
+    do {                                                                          \
+        if (!(grid)) break;                                                       \
+        TimerScope ts(tm, name, st);                                              \
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, __VA_ARGS__);  \
+        if (hipError_t e = hipGetLastError()) return e;                           \
+    } while (0)
+
 __device__ __forceinline__ uint64_t be_dev(const uint8_t *p, int n) {
     uint64_t v = 0;
     for (int k = 0; k < n; k++) v = v << 8 | p[k];
     return v;
+}
+
+// the owner of item i among n: off[p] <= i < off[p + 1]
+__device__ __forceinline__ uint64_t owner_of(const uint64_t *off, uint64_t n, uint64_t i) {
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (off[mid + 1] <= i) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// the hVal of the entry record r: mdLen 2 | md | kLen 2 | key | vLen 4 | vOff 8 | hVal 32
+__device__ __forceinline__ const uint8_t *entry_hval(const uint8_t *r) {
+    const uint32_t ml = ((uint32_t)r[0] << 8) | r[1];
+    const uint8_t *k = r + 2 + ml;
+    const uint32_t kl = ((uint32_t)k[0] << 8) | k[1];
+    return r + 4 + ml + kl + 12;
 }
 
 __device__ __forceinline__ uint64_t ans_slot(const AnsArrays &a, uint64_t x) {
@@ -66,14 +100,13 @@ __device__ __forceinline__ uint64_t framed_u64(uint64_t body) { return 1 + vlen(
 // key, hValue, vLen, metadata (TxEntryToProto, database_protoconv.go:27-49) of
 // the entry record r; the tag and length of the entry are the caller's
 __device__ inline void put_entry_fields(ByteWriter &bw, const uint8_t *r, const AnsEntry &t) {
-    const uint8_t *key = r + 4 + t.ml;
+    const uint8_t *key = r + 4 + t.ml, *hv = entry_hval(r);
     if (t.kl) {
         bw.put8(0x0a);
         bw.varint(t.kl);
         for (uint32_t k = 0; k < t.kl; k++) bw.put8(key[k]);
     }
     {  // hValue: always 32 bytes
-        const uint8_t *hv = key + t.kl + 12;
         uint32_t x[8];
 #pragma unroll
         for (int k = 0; k < 8; k++)

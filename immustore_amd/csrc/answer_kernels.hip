@@ -33,10 +33,6 @@ namespace mh {
 
 namespace {
 
-inline unsigned grid_for(uint64_t threads, unsigned block) {
-    return (unsigned)((threads + block - 1) / block);
-}
-
 // nodes of the flat level layout of a tree of width w (htree.go:85-110)
 __device__ __forceinline__ uint64_t levels_len_dev(uint64_t w) {
     return w ? level_off(w, bits_len(w - 1) + 1) : 0;
@@ -427,65 +423,57 @@ __global__ __launch_bounds__(64) void k_ans_assemble(const AnsArrays a) {
 
 }  // namespace
 
-#define ANS_LAUNCH(name, kernel, grid, block)                                   \
-    do {                                                                        \
-        if (!(grid)) break;                                                     \
-        TimerScope ts(tm, name, st);                                            \
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, a);          \
-        if (hipError_t e = hipGetLastError()) return e;                         \
-    } while (0)
-
 hipError_t launch_ans_heads(hipStream_t st, Timer *tm, const AnsArrays &a) {
-    ANS_LAUNCH("ans_heads", k_ans_heads, grid_for(a.n, 256), 256);
+    MH_LAUNCH("ans_heads", k_ans_heads, grid_for(a.n, 256), 256, a);
     return hipSuccess;
 }
 
 hipError_t launch_ans_popc(hipStream_t st, Timer *tm, const AnsArrays &a) {
-    ANS_LAUNCH("ans_popc", k_ans_popc, grid_for(a.words, 256), 256);
+    MH_LAUNCH("ans_popc", k_ans_popc, grid_for(a.words, 256), 256, a);
     return hipSuccess;
 }
 
 hipError_t launch_ans_compact(hipStream_t st, Timer *tm, const AnsArrays &a) {
-    ANS_LAUNCH("ans_compact", k_ans_compact, grid_for(a.ntx, 256), 256);
+    MH_LAUNCH("ans_compact", k_ans_compact, grid_for(a.ntx, 256), 256, a);
     return hipSuccess;
 }
 
 hipError_t launch_ans_verdict(hipStream_t st, Timer *tm, const AnsArrays &a) {
-    ANS_LAUNCH("ans_verdict", k_ans_verdict, grid_for(a.n, 256), 256);
-    ANS_LAUNCH("ans_link", k_ans_link, grid_for(a.D, 256), 256);
-    ANS_LAUNCH("ans_counts", k_ans_counts, grid_for(a.D, 256), 256);
+    MH_LAUNCH("ans_verdict", k_ans_verdict, grid_for(a.n, 256), 256, a);
+    MH_LAUNCH("ans_link", k_ans_link, grid_for(a.D, 256), 256, a);
+    MH_LAUNCH("ans_counts", k_ans_counts, grid_for(a.D, 256), 256, a);
     return hipSuccess;
 }
 
 hipError_t launch_ans_trees(hipStream_t st, Timer *tm, const AnsArrays &a) {
-    ANS_LAUNCH("ans_trees", k_ans_trees, (unsigned)a.D, 64);
+    MH_LAUNCH("ans_trees", k_ans_trees, (unsigned)a.D, 64, a);
     return hipSuccess;
 }
 
 hipError_t launch_ans_find(hipStream_t st, Timer *tm, const AnsArrays &a) {
-    if (a.E) ANS_LAUNCH("ans_esize", k_ans_esize, grid_for(a.E, 256), 256);
-    ANS_LAUNCH("ans_find", k_ans_find, grid_for(a.n, 4), 256);
+    if (a.E) MH_LAUNCH("ans_esize", k_ans_esize, grid_for(a.E, 256), 256, a);
+    MH_LAUNCH("ans_find", k_ans_find, grid_for(a.n, 4), 256, a);
     return hipSuccess;
 }
 
 hipError_t launch_ans_txsize(hipStream_t st, Timer *tm, const AnsArrays &a) {
-    ANS_LAUNCH("ans_txsize", k_ans_txsize, grid_for(a.D, 256), 256);
+    MH_LAUNCH("ans_txsize", k_ans_txsize, grid_for(a.D, 256), 256, a);
     return hipSuccess;
 }
 
 hipError_t launch_ans_size(hipStream_t st, Timer *tm, const AnsArrays &a) {
-    ANS_LAUNCH("ans_size", k_ans_size, grid_for(a.n, 256), 256);
+    MH_LAUNCH("ans_size", k_ans_size, grid_for(a.n, 256), 256, a);
     return hipSuccess;
 }
 
 hipError_t launch_ans_tx_write(hipStream_t st, Timer *tm, const AnsArrays &a) {
-    ANS_LAUNCH("ans_tx_header", k_ans_tx_header, grid_for(a.D, 256), 256);
-    if (a.E) ANS_LAUNCH("ans_tx_entries", k_ans_tx_entries, grid_for(a.E, 256), 256);
+    MH_LAUNCH("ans_tx_header", k_ans_tx_header, grid_for(a.D, 256), 256, a);
+    if (a.E) MH_LAUNCH("ans_tx_entries", k_ans_tx_entries, grid_for(a.E, 256), 256, a);
     return hipSuccess;
 }
 
 hipError_t launch_ans_assemble(hipStream_t st, Timer *tm, const AnsArrays &a) {
-    ANS_LAUNCH("ans_assemble", k_ans_assemble, (unsigned)a.n, 64);
+    MH_LAUNCH("ans_assemble", k_ans_assemble, (unsigned)a.n, 64, a);
     return hipSuccess;
 }
 

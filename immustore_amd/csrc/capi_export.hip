@@ -3,12 +3,13 @@
 // txs of a store whose tx log, commit log and value logs are resident, in one
 // device pass (the follower's side is capi_repl.hip).
 //
+//   the store: its arguments, where it lies                 store_args_ok, store_resident (capi_txlog.hip)
 //   readTx with the integrity check  :2622, tx.go:388-630   mh_txlog_validate_clog's core
 //   the entries of the valid txs                            k_exp_scan, k_txe_index
 //   decodeOffset, readValueAt's io.EOF  :1429, :3183-3218   k_exp_entry (export_kernels.hip)
 //   "partially truncated"  :2703, :2726; the sizes          k_exp_tx, k_exp_scan
 //   hdr, keys, metadata, hVal of truncated txs, trailer     k_exp_head, k_exp_ent
-//   SHA-256(value) against hVal  :3235, the value bytes     k_exp_values (/ k_exp_copy)
+//   SHA-256(value) against hVal  :3235, the value bytes     k_exp_values (/ k_exp_copy): value_lane (value_store.hpp)
 //   the statuses in Go's order                              k_exp_status
 //
 // The host waits inside the read path, for the number of entries (scratch) and,
@@ -20,14 +21,6 @@
 #include "capi_internal.hpp"
 
 namespace {
-
-bool on_device(const void *q, int device) {
-    hipPointerAttribute_t a;
-    const bool d = hipPointerGetAttributes(&a, q) == hipSuccess && a.type == hipMemoryTypeDevice &&
-                   a.device == device;
-    (void)hipGetLastError();
-    return d;
-}
 
 // MH_EXPORT_ARM=A|B picks the value kernels of a call (tools/bench_export.py
 // times both); the default is the faster one of profiles/export_bench.md
@@ -49,31 +42,15 @@ extern "C" int mh_export_tx_batch(mh_ctx *c, const mh_export_store *s, uint64_t 
         // ---- the arguments alone
         if (!c || !s || !off || !status || (!out && out_cap)) return MH_ERR_ILLEGAL_ARGUMENTS;
         if (first_tx == 0 || count > 0x7fffffffull) return MH_ERR_ILLEGAL_ARGUMENTS;  // (count / 4 workgroups a launch)
+        const mh_answer_store cs = store_prefix(*s);
         const uint64_t N = s->ntx, es = s->clog_entry_size;
-        if (es != 12 && es != 44) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (s->nvlogs > 127 || (s->nvlogs && !s->vlogs)) return MH_ERR_ILLEGAL_ARGUMENTS;  // MaxParallelIO
-        if (N && (!s->txlog || !s->clog)) return MH_ERR_ILLEGAL_ARGUMENTS;
-        for (uint32_t k = 0; k < s->nvlogs; k++) {
-            const mh_export_vlog &v = s->vlogs[k];
-            if (v.end_off < v.first_off) return MH_ERR_ILLEGAL_ARGUMENTS;
-            if (v.end_off > v.first_off && (!v.data || ((uintptr_t)v.data & 3))) return MH_ERR_ILLEGAL_ARGUMENTS;
-        }
+        if (!store_args_ok(cs, s->vlogs, s->nvlogs)) return MH_ERR_ILLEGAL_ARGUMENTS;
         if (count > N || first_tx > N - count + 1) return MH_ERR_TX_NOT_FOUND;  // immustore.go:3000
-        // ---- where the store lies
+        // ---- where the store lies (N > 0 here)
         const int dev = c->device;
-        if (!on_device(s->txlog, dev) || !on_device(s->clog, dev)) return MH_ERR_ILLEGAL_ARGUMENTS;
-        for (uint32_t k = 0; k < s->nvlogs; k++)
-            if (s->vlogs[k].end_off > s->vlogs[k].first_off && !on_device(s->vlogs[k].data, dev))
-                return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (!store_resident(cs, s->vlogs, s->nvlogs, dev)) return MH_ERR_ILLEGAL_ARGUMENTS;
         std::lock_guard<std::mutex> lk_(c->mu);  // txlog_validate_clog_core requires it
         MH_HIP(hipSetDevice(dev));
-        if (!dev_range(s->txlog, s->txlog_len + 256) || !dev_range(s->clog, N * es))
-            return MH_ERR_ILLEGAL_ARGUMENTS;
-        for (uint32_t k = 0; k < s->nvlogs; k++) {
-            const mh_export_vlog &v = s->vlogs[k];
-            if (v.end_off > v.first_off && !dev_range(v.data, v.end_off - v.first_off + 256))
-                return MH_ERR_ILLEGAL_ARGUMENTS;
-        }
         const bool out_dev = out_cap && on_device(out, dev);
         if (out_dev && !dev_range(out, out_cap)) return MH_ERR_ILLEGAL_ARGUMENTS;
         hipStream_t st = c->stream;
@@ -151,8 +128,7 @@ extern "C" int mh_export_tx_batch(mh_ctx *c, const mh_export_store *s, uint64_t 
             // staging is sized by what fits (out in device memory needs neither:
             // the kernels compare off with out_cap themselves, nothing waits)
             MH_HIP(hipStreamSynchronize(st));  // wait 2: the sizes
-            for (uint64_t k = 0; k < n; k++)
-                if (((const uint64_t *)(pin + p_off))[k + 1] <= out_cap) fit = ((const uint64_t *)(pin + p_off))[k + 1];
+            fit = fit_prefix((const uint64_t *)(pin + p_off), n, out_cap);
             MH_HIP(c->s_exp_out.ensure(fit + 64));
         }
 

@@ -351,6 +351,30 @@ struct StreamGuard {
 // The device range [p, p + bytes) lies in one allocation of the current
 // device (hipMemGetAddressRange), or the address is not device memory at all.
 bool dev_range(const void *p, uint64_t bytes);
+// q is device memory, and of `device` (capi_txlog.hip).
+bool on_device(const void *q, int device);
+// A resident store -- the fields mh_answer_store and mh_export_store share,
+// and the value logs of the latter (nvlogs 0: none) -- checked once for
+// mh_verifiable_answer_pb_batch, mh_export_tx_batch and mh_tx_answer_pb_batch
+// (capi_txlog.hip); a call's own checks sit between the two.  By the arguments
+// alone, no HIP call: the entry size, the vLog count, null logs of a store
+// with txs, every vLog's bounds, data and 4-byte alignment.
+bool store_args_ok(const mh_answer_store &s, const mh_export_vlog *vlogs, uint32_t nvlogs);
+// Where it lies: the tx log, the cLog and every non-empty vLog on `device`
+// (decided before the device is touched; then it is made the current one),
+// each inside one allocation, the tx log and the vLogs with the 256 bytes of
+// slack the kernels' block reads run into.
+bool store_resident(const mh_answer_store &s, const mh_export_vlog *vlogs, uint32_t nvlogs, int device);
+inline mh_answer_store store_prefix(const mh_export_store &s) {
+    return {s.txlog, s.txlog_len, s.clog, s.ntx, s.clog_entry_size, s.max_entries, s.max_key_len};
+}
+// the answers that fit are a prefix of the batch's bytes
+inline uint64_t fit_prefix(const uint64_t *off, uint64_t n, uint64_t out_cap) {
+    uint64_t fit = 0;
+    for (uint64_t p = 0; p < n; p++)
+        if (off[p + 1] <= out_cap) fit = off[p + 1];
+    return fit;
+}
 // The copy chunks of a log of len bytes at `log`: chunk k is bytes [cut[k],
 // cut[k + 1]).  One chunk for a resident log or one below 16 MiB, else
 // txlog_weights() (5 : 2 : 1) for a pinned log and 3 : 1 for a pageable one,
@@ -715,6 +739,31 @@ struct Layout {
         total = (total + bytes + 255) & ~255ull;
         return o;
     }
+};
+
+// The read-set stage of mh_verifiable_answer_pb_batch and mh_tx_answer_pb_batch
+// (answer_read.hip): the txs a batch reads, every distinct one read and
+// re-hashed once, the verdicts, links and entry counts of the asked ones.
+// t->mu (if any) and c->mu are held, the device is set and a StreamGuard
+// covers c->stream.  Three steps with the caller between them; each takes the
+// Layout of one scratch buffer with the caller's own columns already in it,
+// adds the stage's, makes the buffer and binds the stage's arrays of `a`:
+//   requests(n, L)  c->s_ans      then the caller uploads kind / tx / since and its own
+//   heads()         wait 1: D, D1 = max(D, 1) distinct txs
+//   reads(S)        c->s_ans_tx   zeroed up to the re-hash's scratch; leaf_off scanned
+struct AnsRead {
+    mh_ctx *c;
+    const mh_answer_store &s;
+    AnsArrays &a;
+    uint8_t *base = nullptr, *sb = nullptr;  // s_ans, s_ans_tx
+    volatile uint64_t *hw = nullptr;         // p_small, where the waits read
+    uint64_t W = 1, D1 = 1;
+    uint64_t b_kind = 0, b_tx = 0, b_since = 0, b_dst = 0, b_dpo = 0, b_off = 0, b_dps = 0;
+    uint8_t *scan = nullptr, *dscan = nullptr;  // scan temp of max(n, W) / D1 items
+    size_t scan_bytes = 0, dscan_bytes = 0;
+    int requests(uint64_t n, Layout &L);
+    int heads();
+    int reads(Layout &S);
 };
 
 // ---------------------------------------------------------------- many trees

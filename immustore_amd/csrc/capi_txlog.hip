@@ -2,7 +2,8 @@
 // mh_txlog_validate_resident and txlog_validate_parsed (the multi-device
 // call's entry), all three over one driver, TxlogCall, plus the pieces the
 // cLog call (capi_clog.hip) shares with it: copy-chunk cuts, the caller's
-// output arrays (TxlogOutputs), the device range check.
+// output arrays (TxlogOutputs), the device range check -- and with it the
+// resident-store check of the answer, export and tx-answer calls.
 //
 // The host hop is in txlog_hop.hip; every SHA-256 runs in tx_kernels.hip,
 // txlog_wave.hip, txlog_lanes.hip and htree_kernels.hip.
@@ -35,6 +36,41 @@ bool dev_range(const void *p, uint64_t bytes) {
     }
     const uintptr_t b = (uintptr_t)base, d = (uintptr_t)p;
     return d >= b && d - b <= size && bytes <= size - (d - b);
+}
+
+bool on_device(const void *q, int device) {
+    hipPointerAttribute_t a;
+    const bool d = hipPointerGetAttributes(&a, q) == hipSuccess && a.type == hipMemoryTypeDevice &&
+                   a.device == device;
+    (void)hipGetLastError();
+    return d;
+}
+
+bool store_args_ok(const mh_answer_store &s, const mh_export_vlog *vlogs, uint32_t nvlogs) {
+    if (s.clog_entry_size != 12 && s.clog_entry_size != 44) return false;
+    if (nvlogs > 127 || (nvlogs && !vlogs)) return false;  // MaxParallelIO
+    if (s.ntx && (!s.txlog || !s.clog)) return false;
+    for (uint32_t k = 0; k < nvlogs; k++) {
+        const mh_export_vlog &v = vlogs[k];
+        if (v.end_off < v.first_off) return false;
+        if (v.end_off > v.first_off && (!v.data || ((uintptr_t)v.data & 3))) return false;
+    }
+    return true;
+}
+
+bool store_resident(const mh_answer_store &s, const mh_export_vlog *vlogs, uint32_t nvlogs, int device) {
+    if (s.ntx && (!on_device(s.txlog, device) || !on_device(s.clog, device))) return false;
+    for (uint32_t k = 0; k < nvlogs; k++)
+        if (vlogs[k].end_off > vlogs[k].first_off && !on_device(vlogs[k].data, device)) return false;
+    // (memory of another place is refused before the device is touched at all)
+    if (hipSetDevice(device) != hipSuccess) return false;
+    if (s.ntx && (!dev_range(s.txlog, s.txlog_len + 256) || !dev_range(s.clog, s.ntx * s.clog_entry_size)))
+        return false;
+    for (uint32_t k = 0; k < nvlogs; k++) {
+        const mh_export_vlog &v = vlogs[k];
+        if (v.end_off > v.first_off && !dev_range(v.data, v.end_off - v.first_off + 256)) return false;
+    }
+    return true;
 }
 
 // Where a kernel can store the caller's output array p of `bytes`: p itself

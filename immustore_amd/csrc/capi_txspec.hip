@@ -4,14 +4,16 @@
 // db.VerifiableTxByID (:1462-1528), with db.serializeTx (:1080-1231) and
 // ImmuStore.ReadValue (immustore.go:3149-3240) run on the device.
 //
-//   the reads of a request, every distinct tx once,      the answer path's kernels
-//     ReadTx's re-hash, verdicts, links, entry index     (capi_answer.hip's list)
+//   the store: its arguments, where it lies              store_args_ok, store_resident (capi_txlog.hip)
+//   the reads of a request, every distinct tx once,      AnsRead, the answer path's read-set
+//     ReadTx's re-hash, verdicts, links                  stage (capi_answer.hip's list)
+//   entry index                                          k_txe_index
 //   variants and groups of the batch                     the host, from the requests alone
 //   serializeTx's switch, ReadValue up to the read       k_txs_plan (txspec_kernels.hip)
 //   DualProof sizes and statuses                         k_pb_dual1_size over the RankWindow
 //   sizes, one scan                                      k_txs_vsize, k_txs_size
 //   schema.Tx once per variant                           k_txs_header, k_txs_entries
-//   SHA-256(value) against hVal, the value bytes         k_txs_values (/ k_txs_copy)
+//   SHA-256(value) against hVal, the value bytes         k_txs_values (/ k_txs_copy): value_lane (value_store.hpp)
 //   the answers, the DualProofs, the statuses            k_txs_assemble, k_pb_dual1_write, k_txs_status
 //
 // The host waits for the number of distinct txs, inside the read path, for the
@@ -25,14 +27,6 @@
 #include "capi_internal.hpp"
 
 namespace {
-
-bool on_dev(const void *q, int device) {
-    hipPointerAttribute_t a;
-    const bool d = hipPointerGetAttributes(&a, q) == hipSuccess && a.type == hipMemoryTypeDevice &&
-                   a.device == device;
-    (void)hipGetLastError();
-    return d;
-}
 
 // req.EntriesSpec's three actions as a variant's mode; false: outside the enum
 bool txs_mode(const mh_tx_answer_batch *b, uint64_t p, uint8_t *mode, bool *resolve) {
@@ -75,16 +69,10 @@ extern "C" int mh_tx_answer_pb_batch(mh_ctx *c, mh_ahtree *t, const mh_export_st
             !b->has_spec || !b->kv_action || !b->z_action || !b->sql_action)
             return MH_ERR_ILLEGAL_ARGUMENTS;
         if (n > 0x7fffffffull) return MH_ERR_ILLEGAL_ARGUMENTS;  // hipcub's int item count
-        const uint64_t N = s->ntx, es = s->clog_entry_size;
-        if (es != 12 && es != 44) return MH_ERR_ILLEGAL_ARGUMENTS;
+        const mh_answer_store cs = store_prefix(*s);
+        const uint64_t N = s->ntx;
+        if (!store_args_ok(cs, s->vlogs, s->nvlogs)) return MH_ERR_ILLEGAL_ARGUMENTS;
         if (N >= (1ull << 36)) return MH_ERR_ILLEGAL_ARGUMENTS;  // the bitmap's words are scanned as ints
-        if (s->nvlogs > 127 || (s->nvlogs && !s->vlogs)) return MH_ERR_ILLEGAL_ARGUMENTS;  // MaxParallelIO
-        if (N && (!s->txlog || !s->clog)) return MH_ERR_ILLEGAL_ARGUMENTS;
-        for (uint32_t k = 0; k < s->nvlogs; k++) {
-            const mh_export_vlog &v = s->vlogs[k];
-            if (v.end_off < v.first_off) return MH_ERR_ILLEGAL_ARGUMENTS;
-            if (v.end_off > v.first_off && (!v.data || ((uintptr_t)v.data & 3))) return MH_ERR_ILLEGAL_ARGUMENTS;
-        }
         if (t && t->ctx != c) return MH_ERR_ILLEGAL_ARGUMENTS;
         // ---- the requests: variants (tx, actions) and groups (tx, classes read)
         std::vector<uint8_t> mode(n);
@@ -133,18 +121,8 @@ extern "C" int mh_tx_answer_pb_batch(mh_ctx *c, mh_ahtree *t, const mh_export_st
         std::lock_guard<std::mutex> lkc_(c->mu);
         const int dev = c->device;
         MH_HIP(hipSetDevice(dev));
-        if (N) {
-            if (!on_dev(s->txlog, dev) || !on_dev(s->clog, dev)) return MH_ERR_ILLEGAL_ARGUMENTS;
-            if (!dev_range(s->txlog, s->txlog_len + 256) || !dev_range(s->clog, N * es))
-                return MH_ERR_ILLEGAL_ARGUMENTS;
-        }
-        for (uint32_t k = 0; k < s->nvlogs; k++) {
-            const mh_export_vlog &v = s->vlogs[k];
-            if (v.end_off > v.first_off &&
-                (!on_dev(v.data, dev) || !dev_range(v.data, v.end_off - v.first_off + 256)))
-                return MH_ERR_ILLEGAL_ARGUMENTS;
-        }
-        const bool out_dev = out_cap && on_dev(out, dev);
+        if (!store_resident(cs, s->vlogs, s->nvlogs, dev)) return MH_ERR_ILLEGAL_ARGUMENTS;
+        const bool out_dev = out_cap && on_device(out, dev);
         if (out_dev && !dev_range(out, out_cap)) return MH_ERR_ILLEGAL_ARGUMENTS;
         hipStream_t st = c->stream;
         Timer *tm = c->tm();
@@ -153,91 +131,39 @@ extern "C" int mh_tx_answer_pb_batch(mh_ctx *c, mh_ahtree *t, const mh_export_st
         // ---- requests up, the read set (the answer path's, every kind its MH_ANS_TX)
         AnsArrays a{};
         TxsArrays x{};
-        a.txlog = s->txlog, a.clog = s->clog, a.txlog_len = s->txlog_len, a.ntx = N, a.es = (uint32_t)es;
-        a.n = n;
-        a.words = (N + 63) / 64;
+        AnsRead r{c, cs, a};
         x.V = V, x.nvlogs = s->nvlogs, x.now = b->now_unix;
-        const uint64_t W = std::max<uint64_t>(a.words, 1), nv = std::max<uint32_t>(s->nvlogs, 1);
-        const size_t scan_bytes = pb_scan_temp_bytes(std::max(n, W));
+        const uint64_t nv = std::max<uint32_t>(s->nvlogs, 1);
         Layout L;
-        const uint64_t b_kind = L.add(n), b_tx = L.add(n * 8), b_since = L.add(n * 8),
-                       b_zoff = L.add((n + 1) * 8), b_pre = L.add(n * 4),
-                       b_hs = L.add(n * sizeof(mh_tx_header)), b_ht = L.add(n * sizeof(mh_tx_header)),
-                       b_leaf = L.add(n * 8), b_dst = L.add(n * 4), b_dpo = L.add((n + 1) * 8),
-                       b_sz = L.add(n * 8), b_dpos = L.add(n * 8), b_off = L.add((n + 1) * 8),
-                       b_st = L.add(n * 4), b_bits = L.add(W * 8), b_wcnt = L.add(W * 8),
-                       b_rank = L.add((W + 1) * 8), b_scan = L.add(scan_bytes),
-                       b_dps = L.add(pb_dual_v1_scratch_bytes(n)), b_xk = L.add(n), b_rv = L.add(n * 4),
+        const uint64_t b_zoff = L.add((n + 1) * 8), b_xk = L.add(n), b_rv = L.add(n * 4),
                        b_wst = L.add(n * 4), b_vl = L.add(nv * sizeof(ExpVlog));
-        MH_HIP(c->s_ans.ensure(L.total));
-        uint8_t *base = c->s_ans.as<uint8_t>();
+        if (int e = r.requests(n, L)) return e;
+        uint8_t *base = r.base;
         auto U = [&](uint64_t o) { return (uint64_t *)(base + o); };
         auto h2d = [&](uint8_t *dst, const void *p, uint64_t bytes) -> hipError_t {
             return bytes ? hipMemcpyAsync(dst, p, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
         };
-        MH_HIP(hipMemsetAsync(base + b_kind, 0, n, st));  // MH_ANS_TX
+        MH_HIP(hipMemsetAsync(base + r.b_kind, 0, n, st));  // MH_ANS_TX
         MH_HIP(hipMemsetAsync(base + b_zoff, 0, (n + 1) * 8, st));
-        MH_HIP(hipMemsetAsync(base + b_dpo, 0, (n + 1) * 8, st));
-        MH_HIP(hipMemsetAsync(base + b_dst, 0, n * 4, st));
-        MH_HIP(h2d(base + b_tx, b->tx, n * 8));
-        MH_HIP(h2d(base + b_since, since.data(), n * 8));
+        MH_HIP(hipMemsetAsync(base + r.b_dpo, 0, (n + 1) * 8, st));
+        MH_HIP(hipMemsetAsync(base + r.b_dst, 0, n * 4, st));
+        MH_HIP(h2d(base + r.b_tx, b->tx, n * 8));
+        MH_HIP(h2d(base + r.b_since, since.data(), n * 8));
         MH_HIP(h2d(base + b_xk, b->kind, n));
         MH_HIP(h2d(base + b_rv, rv.data(), n * 4));
         static_assert(sizeof(ExpVlog) == sizeof(mh_export_vlog), "the vLog table goes up as it is");
         MH_HIP(h2d(base + b_vl, s->vlogs, s->nvlogs * sizeof(ExpVlog)));
-        a.kind = base + b_kind, a.tx = U(b_tx), a.since = U(b_since);
         a.key_off = a.entry_off = U(b_zoff);
         a.keys = a.entries = base;
-        a.pre = (int32_t *)(base + b_pre), a.hs = (MhTxHeader *)(base + b_hs);
-        a.ht = (MhTxHeader *)(base + b_ht), a.leaf = U(b_leaf);
-        a.dst = (int32_t *)(base + b_dst), a.dp_off = U(b_dpo), a.sizes = U(b_sz), a.dpos = U(b_dpos);
-        a.off = U(b_off), a.status = (int32_t *)(base + b_st);
-        a.bits = U(b_bits), a.wcnt = U(b_wcnt), a.rank = U(b_rank);
         x.kind = base + b_xk, x.rv = (const uint32_t *)(base + b_rv), x.wst = (int32_t *)(base + b_wst);
         x.vlogs = (const ExpVlog *)(base + b_vl);
-        uint8_t *scan = base + b_scan;
-        MH_HIP(hipMemsetAsync(a.bits, 0, W * 8, st));
-        MH_HIP(hipMemsetAsync(a.wcnt, 0, W * 8, st));
-        MH_HIP(launch_ans_heads(st, tm, a));
-        if (a.words) MH_HIP(launch_ans_popc(st, tm, a));
-        MH_HIP(scan_offsets_u64(st, W, a.wcnt, a.rank, scan, scan_bytes));
-        MH_HIP(c->p_small.ensure(64));
-        volatile uint64_t *hw = c->p_small.as<volatile uint64_t>();
-        MH_HIP(hipMemcpyAsync((void *)hw, a.rank + W, 8, hipMemcpyDeviceToHost, st));
-        MH_HIP(hipStreamSynchronize(st));  // wait 1: the distinct txs read
-        const uint64_t D = a.D = hw[0], D1 = std::max<uint64_t>(D, 1);
-        if (D > 0x7fffffffull) return MH_ERR_ILLEGAL_ARGUMENTS;  // hipcub's int item count; grids of D blocks
+        if (int e = r.heads()) return e;  // wait 1: the distinct txs read
+        const uint64_t D = a.D;
 
         // ---- every distinct tx read and re-hashed once
-        const size_t dscan_bytes = pb_scan_temp_bytes(D1);
         Layout S;
-        const uint64_t d_ids = S.add(D1 * 8), d_cl = S.add(D1 * es),
-                       d_hd = S.add(D1 * sizeof(mh_tx_header)), d_alh = S.add(D1 * 32),
-                       d_in = S.add(D1 * 32), d_rst = S.add(D1 * 4), d_lnk = S.add(D1),
-                       d_fl = S.add(D1 * 4), d_ec = S.add(D1 * 8), d_nc = S.add(D1 * 8),
-                       d_lo = S.add((D1 + 1) * 8), d_es = S.add(D1 * 8),
-                       d_am = S.add(D1 * kTxInnerStride), d_scan = S.add(dscan_bytes);
-        MH_HIP(c->s_ans_tx.ensure(S.total));
-        uint8_t *sb = c->s_ans_tx.as<uint8_t>();
-        auto Vq = [&](uint64_t o) { return (uint64_t *)(sb + o); };
-        a.ids = Vq(d_ids), a.gclog = sb + d_cl, a.hd = (MhTxHeader *)(sb + d_hd);
-        a.alh = sb + d_alh, a.inner = sb + d_in, a.rst = (int32_t *)(sb + d_rst), a.lnk = sb + d_lnk;
-        a.flags = (uint32_t *)(sb + d_fl), a.ecnt = Vq(d_ec), a.ncnt = Vq(d_nc);
-        a.leaf_off = Vq(d_lo), a.ent_start = Vq(d_es);
-        MH_HIP(hipMemsetAsync(sb, 0, d_am, st));  // (no slot: the scans below still read one item)
-        if (D) {
-            MH_HIP(launch_ans_compact(st, tm, a));
-            // ReadTx with the integrity check, per distinct tx (its own waits; c->mu is held)
-            if (int e = txlog_validate_clog_core(c, s->txlog, s->txlog_len, a.gclog, D, (uint32_t)es,
-                                                 s->max_entries, s->max_key_len, a.hd, a.alh, a.rst,
-                                                 nullptr, nullptr))
-                return e;
-            hw = c->p_small.as<volatile uint64_t>();  // (the read path may have grown it)
-            MH_HIP(launch_tx_alh(st, tm, D, a.hd, s->txlog, nullptr, sb + d_am, nullptr, nullptr,
-                                 a.inner, a.alh, nullptr));
-        }
-        MH_HIP(launch_ans_verdict(st, tm, a));
-        MH_HIP(scan_offsets_u64(st, D1, a.ecnt, Vq(d_lo), sb + d_scan, dscan_bytes));
+        if (int e = r.reads(S)) return e;
+        volatile uint64_t *hw = r.hw;
 
         // ---- the variants: their slots, their items
         const size_t vscan_bytes = pb_scan_temp_bytes(V);
@@ -294,17 +220,14 @@ extern "C" int mh_tx_answer_pb_batch(mh_ctx *c, mh_ahtree *t, const mh_export_st
         RankWindow win{a.bits, a.rank, a.rst, a.lnk, N, a.dpos};
         if (t)
             MH_HIP(launch_pb_dual_v1_ranked(st, tm, 1, t->dlog.as<uint8_t>(), t->size, n, a.hs, a.ht,
-                                            s->txlog, win, a.alh, a.inner, nullptr, U(b_dpo),
-                                            (int32_t *)(base + b_dst), base + b_dps));
+                                            s->txlog, win, a.alh, a.inner, nullptr, U(r.b_dpo),
+                                            (int32_t *)(base + r.b_dst), base + r.b_dps));
         MH_HIP(launch_txs_size(st, tm, a, x));
-        MH_HIP(scan_offsets_u64(st, n, a.sizes, U(b_off), scan, scan_bytes));
+        MH_HIP(scan_offsets_u64(st, n, a.sizes, U(r.b_off), r.scan, r.scan_bytes));
         MH_HIP(hipMemcpyAsync(off, a.off, (n + 1) * 8, hipMemcpyDeviceToHost, st));
         MH_HIP(hipMemcpyAsync((void *)hw, x.vpos + V, 8, hipMemcpyDeviceToHost, st));
         MH_HIP(hipStreamSynchronize(st));  // wait 3: the sizes
-        const uint64_t shared_bytes = hw[0];
-        uint64_t fit = 0;  // the answers that fit are a prefix of the batch's bytes
-        for (uint64_t p = 0; p < n; p++)
-            if (off[p + 1] <= out_cap) fit = off[p + 1];
+        const uint64_t shared_bytes = hw[0], fit = fit_prefix(off, n, out_cap);
 
         // ---- write: schema.Tx once per variant, the values hashed and stored, the answers
         Layout O;
@@ -323,8 +246,8 @@ extern "C" int mh_tx_answer_pb_batch(mh_ctx *c, mh_ahtree *t, const mh_export_st
         MH_HIP(launch_txs_assemble(st, tm, a, x));
         if (t)
             MH_HIP(launch_pb_dual_v1_ranked(st, tm, 2, t->dlog.as<uint8_t>(), t->size, n, a.hs, a.ht,
-                                            s->txlog, win, a.alh, a.inner, a.out, U(b_dpo), x.wst,
-                                            base + b_dps));
+                                            s->txlog, win, a.alh, a.inner, a.out, U(r.b_dpo), x.wst,
+                                            base + r.b_dps));
         MH_HIP(launch_txs_status(st, tm, a, x));
         if (!out_dev && fit) MH_HIP(hipMemcpyAsync(out, a.out, fit, hipMemcpyDeviceToHost, st));
         MH_HIP(hipMemcpyAsync(status, a.status, n * 4, hipMemcpyDeviceToHost, st));

@@ -13,7 +13,8 @@
 //   header and trailer                           k_exp_head, one tx per wave
 //   key, KVMetadata.Bytes(), vLen / the hVal     k_exp_ent, one entry per lane
 //   SHA-256 of the value against hVal, its copy  k_exp_values<true> (arm A), or
-//                                                k_exp_values<false> + k_exp_copy (arm B)
+//                                                k_exp_values<false> + k_exp_copy (arm B):
+//                                                value_lane (value_store.hpp) over ExpValues
 //   the statuses in ExportTx's order             k_exp_status, one tx per lane
 //
 // A tx record (immustore.go:1812-1924): id 8 | ts 8 | blTxID 8 | blRoot 32 |
@@ -25,7 +26,8 @@
 // rebuilt Eh is taken.
 //
 // Cost shape: k_exp_values is the call's hashing, k_sha_varlen's loop with the
-// stores added.  A lane runs (vLen + 9 + 63) / 64 compressions; lanes take
+// stores added (value_lane, shared with txspec_kernels.hip's k_txs_values).
+// A lane runs (vLen + 9 + 63) / 64 compressions; lanes take
 // values in length-class order, so a wave runs no idle blocks.  In arm A the
 // lane also stores each 64-byte block it has just turned into message words:
 // one v_perm_b32 per dword puts them on the destination's dword grid (the
@@ -45,16 +47,6 @@ namespace mh {
 
 namespace {
 
-inline unsigned grid_for(uint64_t threads, unsigned block) {
-    return (unsigned)((threads + block - 1) / block);
-}
-
-__device__ __forceinline__ uint64_t xp_be(const uint8_t *p, int n) {
-    uint64_t v = 0;
-    for (int k = 0; k < n; k++) v = v << 8 | p[k];
-    return v;
-}
-
 __device__ __forceinline__ void xp_put(uint8_t *&o, uint64_t v, int n) {  // big-endian, n bytes
     for (int k = n - 1; k >= 0; k--) *o++ = (uint8_t)(v >> (8 * k));
 }
@@ -68,28 +60,17 @@ struct ExpRec {
 
 __device__ __forceinline__ ExpRec exp_rec(const ExpArrays &a, uint64_t t) {
     ExpRec x;
-    x.r = a.txlog + xp_be(a.clog + t * a.es, 8);
-    x.ver = (uint32_t)xp_be(x.r + 88, 2);
-    x.sml = x.ver ? (uint32_t)xp_be(x.r + 90, 2) : 0;
+    x.r = a.txlog + be_dev(a.clog + t * a.es, 8);
+    x.ver = (uint32_t)be_dev(x.r + 88, 2);
+    x.sml = x.ver ? (uint32_t)be_dev(x.r + 90, 2) : 0;
     x.md = x.r + 92;
-    x.ne = x.ver ? (uint32_t)xp_be(x.r + 92 + x.sml, 4) : (uint32_t)xp_be(x.r + 90, 2);
+    x.ne = x.ver ? (uint32_t)be_dev(x.r + 92 + x.sml, 4) : (uint32_t)be_dev(x.r + 90, 2);
     return x;
 }
 
 // len(TxHeader.Bytes()), tx.go:103-164
 __device__ __forceinline__ uint32_t exp_hdr_len(uint32_t ver, uint32_t mdl) {
     return ver ? 128 + mdl : 124;
-}
-
-// the tx that owns entry e: leaf_off[p] <= e < leaf_off[p + 1]
-__device__ __forceinline__ uint64_t exp_owner(const ExpArrays &a, uint64_t e) {
-    uint64_t lo = 0, hi = a.n;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (a.leaf_off[mid + 1] <= e) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
 }
 
 // the blob of tx p is written: no entry failed before any hash, and it fits
@@ -158,7 +139,7 @@ __global__ __launch_bounds__(256) void k_exp_entry(const ExpArrays a) {
     const uint8_t *r = a.txlog + a.rec_off[e];
     const uint32_t ml = rd_be16(r), kl = rd_be16(r + 2 + ml);
     const uint8_t *f = r + 4 + ml + kl;
-    const uint64_t vl = xp_be(f, 4), voff = xp_be(f + 4, 8);
+    const uint64_t vl = be_dev(f, 4), voff = be_dev(f + 4, 8);
     const uint32_t id = (uint32_t)(voff >> 56);
     const uint64_t at = voff & ~(0xffull << 55);
     uint8_t cls = kExpAvail;
@@ -210,7 +191,7 @@ __global__ __launch_bounds__(256) void k_exp_tx(const ExpArrays a) {
             const uint8_t *f = a.txlog + a.rec_off[e];
             const uint32_t ml = rd_be16(f), kl = rd_be16(f + 2 + ml);
             a.skip[e] = !hash;
-            a.vlen[e] = hash ? xp_be(f + 4 + ml + kl, 4) : 0;
+            a.vlen[e] = hash ? be_dev(f + 4 + ml + kl, 4) : 0;
             v = a.esz[e];
         }
         const unsigned long long own = v;
@@ -279,11 +260,11 @@ __global__ __launch_bounds__(256) void k_exp_head(const ExpArrays a) {
 __global__ __launch_bounds__(256) void k_exp_ent(const ExpArrays a) {
     const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= a.E) return;
-    const uint64_t p = exp_owner(a, e);
+    const uint64_t p = owner_of(a.leaf_off, a.n, e);
     if (!exp_written(a, p)) return;
     const uint8_t *r = a.txlog + a.rec_off[e];
     const uint32_t ml = rd_be16(r), kl = rd_be16(r + 2 + ml);
-    const uint8_t *key = r + 4 + ml, *f = key + kl;
+    const uint8_t *key = r + 4 + ml, *f = key + kl, *hv = entry_hval(r);
     uint8_t *o = exp_entry_at(a, p, e, a.ver[e]);
     xp_put(o, kl, 2);
     for (uint32_t k = 0; k < kl; k++) *o++ = key[k];
@@ -291,67 +272,45 @@ __global__ __launch_bounds__(256) void k_exp_ent(const ExpArrays a) {
     xp_put(o, cml, 2);
     o += cml;
     if (a.cls[e] == kExpAvail) {
-        xp_put(o, xp_be(f, 4), 4);
+        xp_put(o, be_dev(f, 4), 4);
     } else {
         xp_put(o, 32, 4);
-        for (int k = 0; k < 32; k++) *o++ = f[12 + k];
+        for (int k = 0; k < 32; k++) *o++ = hv[k];
     }
 }
 
-// One value per lane, in perm order (or input order when perm is null):
-// SHA-256 of vsrc[i][0 .. vlen[i]) against the hVal its entry stores
-// (readValueAt, immustore.go:3235); a difference leaves the entry's index in
-// vbad of its tx (the lowest one).  COPY: a value whose blob is written is
-// stored to its place block by block from the message words.
+// value_lane (value_store.hpp) over the entries, their owners the txs: a digest
+// that differs leaves the entry's index in vbad of its tx (the lowest one).
+// COPY: a value whose blob is written is stored to its place; else the stores
+// are compiled out.
+template <bool COPY>
+struct ExpValues {
+    static constexpr bool stores = COPY;
+    const ExpArrays &a;
+    uint64_t n;
+    const uint8_t *idle;
+    __device__ __forceinline__ bool skip(uint64_t e) const { return a.skip[e]; }
+    __device__ __forceinline__ const uint8_t *src(uint64_t e) const { return a.vsrc[e]; }
+    __device__ __forceinline__ uint64_t len(uint64_t e) const { return a.vlen[e]; }
+    __device__ __forceinline__ uint64_t owner(uint64_t e) const {
+        return owner_of(a.leaf_off, a.n, e);
+    }
+    __device__ __forceinline__ bool place(uint64_t e, uint64_t p, uint64_t L, uint8_t *&to) const {
+        if (!(L && exp_written(a, p))) return false;
+        to = exp_entry_at(a, p, e, a.ver[e]) + a.esz[e] - L;
+        return true;
+    }
+    __device__ __forceinline__ const uint8_t *record(uint64_t e, uint64_t) const {
+        return a.txlog + a.rec_off[e];
+    }
+    __device__ __forceinline__ void differs(uint64_t e, uint64_t p) const {
+        atomicMin(a.vbad + p, (uint32_t)(e - a.leaf_off[p]));
+    }
+};
+
 template <bool COPY>
 __global__ __launch_bounds__(256) void k_exp_values(const ExpArrays a, const uint32_t *__restrict__ perm) {
-    const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool valid = g < a.E;
-    const uint64_t gc = valid ? g : a.E - 1;
-    const uint64_t i = perm ? (uint64_t)perm[gc] : gc;
-    const bool live = valid && !a.skip[i];
-    const uint64_t L = live ? a.vlen[i] : 0;
-    const uint8_t *src = live ? a.vsrc[i] : a.txlog;
-    const uint32_t nb = live ? (uint32_t)((L + 72) >> 6) : 0u;
-    const uint32_t nbmax = wave_max_u32(nb);
-    uint64_t p = 0;
-    ExpDst d{};
-    uint32_t *al = nullptr, sel = 0, carry = 0;
-    bool copy = false;
-    if (live) {
-        p = exp_owner(a, i);
-        if (COPY && L && exp_written(a, p)) {
-            copy = true;
-            d = exp_dst(exp_entry_at(a, p, i, a.ver[i]) + a.esz[i] - L, L);
-            al = reinterpret_cast<uint32_t *>(d.dst - d.g);
-            sel = be_sel(d.g);
-            for (uint64_t m = 0; m < d.head; m++) d.dst[m] = src[m];
-            for (uint64_t m = d.tail; m < L; m++) d.dst[m] = src[m];
-        }
-    }
-    MsgWalk mw;
-    mw.init(src, L);
-    State s;
-    s.init();
-#pragma unroll 1
-    for (uint32_t b = 0; b < nbmax; b++) {
-        const bool on = b < nb;
-        uint32_t w[16];
-        mw.block(b, nb, on, __ballot(on && b + 2 >= nb) == 0, w);
-        if (COPY && copy && on) {
-            store_block(al, b, w, carry, sel, d.q0, d.q1);
-            carry = w[15];
-        }
-        if (on) compress(s, w);
-    }
-    if (!live) return;
-    const uint8_t *r = a.txlog + a.rec_off[i];
-    const uint32_t ml = rd_be16(r), kl = rd_be16(r + 2 + ml);
-    const uint8_t *hv = r + 4 + ml + kl + 12;
-    uint32_t diff = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) diff |= bswap(rd_le32(hv + 4 * j)) ^ s.h[j];
-    if (diff) atomicMin(a.vbad + p, (uint32_t)(i - a.leaf_off[p]));
+    value_lane(ExpValues<COPY>{a, a.E, a.txlog}, perm);
 }
 
 // arm B's copy: one wave per value whose blob is written
@@ -359,7 +318,7 @@ __global__ __launch_bounds__(256) void k_exp_copy(const ExpArrays a) {
     const uint64_t e = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (e >= a.E || a.skip[e] || !a.vlen[e]) return;  // wave-uniform
-    const uint64_t p = exp_owner(a, e);
+    const uint64_t p = owner_of(a.leaf_off, a.n, e);
     if (!exp_written(a, p)) return;
     const uint64_t L = a.vlen[e];
     wave_copy(exp_entry_at(a, p, e, a.ver[e]) + a.esz[e] - L, a.vsrc[e], L, lane);
@@ -383,14 +342,6 @@ __global__ __launch_bounds__(256) void k_exp_status(const ExpArrays a) {
 
 }  // namespace
 
-#define EXP_LAUNCH(name, kernel, grid, ...)                                       \
-    do {                                                                          \
-        if (!(grid)) break;                                                       \
-        TimerScope ts(tm, name, st);                                              \
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, __VA_ARGS__);    \
-        if (hipError_t e = hipGetLastError()) return e;                           \
-    } while (0)
-
 hipError_t launch_exp_counts(hipStream_t st, Timer *tm, const ExpArrays &a) {
     TimerScope ts(tm, "exp_counts", st);
     hipLaunchKernelGGL(k_exp_scan<true>, dim3(1), dim3(1024), 0, st, a);
@@ -398,36 +349,36 @@ hipError_t launch_exp_counts(hipStream_t st, Timer *tm, const ExpArrays &a) {
 }
 
 hipError_t launch_exp_entries(hipStream_t st, Timer *tm, const ExpArrays &a) {
-    EXP_LAUNCH("exp_entry", k_exp_entry, grid_for(a.E, 256), a);
+    MH_LAUNCH("exp_entry", k_exp_entry, grid_for(a.E, 256), 256, a);
     return hipSuccess;
 }
 
 hipError_t launch_exp_sizes(hipStream_t st, Timer *tm, const ExpArrays &a) {
-    EXP_LAUNCH("exp_tx", k_exp_tx, grid_for(a.n, 4), a);
+    MH_LAUNCH("exp_tx", k_exp_tx, grid_for(a.n, 4), 256, a);
     TimerScope ts(tm, "exp_offsets", st);
     hipLaunchKernelGGL(k_exp_scan<false>, dim3(1), dim3(1024), 0, st, a);
     return hipGetLastError();
 }
 
 hipError_t launch_exp_frame(hipStream_t st, Timer *tm, const ExpArrays &a) {
-    EXP_LAUNCH("exp_head", k_exp_head, grid_for(a.n, 4), a);
-    EXP_LAUNCH("exp_keys", k_exp_ent, grid_for(a.E, 256), a);
+    MH_LAUNCH("exp_head", k_exp_head, grid_for(a.n, 4), 256, a);
+    MH_LAUNCH("exp_keys", k_exp_ent, grid_for(a.E, 256), 256, a);
     return hipSuccess;
 }
 
 hipError_t launch_exp_values(hipStream_t st, Timer *tm, const ExpArrays &a, const uint32_t *perm,
                              char arm) {
     if (arm == 'A') {
-        EXP_LAUNCH("exp_values_store", k_exp_values<true>, grid_for(a.E, 256), a, perm);
+        MH_LAUNCH("exp_values_store", k_exp_values<true>, grid_for(a.E, 256), 256, a, perm);
     } else {
-        EXP_LAUNCH("exp_values_hash", k_exp_values<false>, grid_for(a.E, 256), a, perm);
-        EXP_LAUNCH("exp_copy", k_exp_copy, grid_for(a.E, 4), a);
+        MH_LAUNCH("exp_values_hash", k_exp_values<false>, grid_for(a.E, 256), 256, a, perm);
+        MH_LAUNCH("exp_copy", k_exp_copy, grid_for(a.E, 4), 256, a);
     }
     return hipSuccess;
 }
 
 hipError_t launch_exp_status(hipStream_t st, Timer *tm, const ExpArrays &a) {
-    EXP_LAUNCH("exp_status", k_exp_status, grid_for(a.n, 256), a);
+    MH_LAUNCH("exp_status", k_exp_status, grid_for(a.n, 256), 256, a);
     return hipSuccess;
 }
 

@@ -29,9 +29,9 @@
 // request asks for is written straight into that answer; one that several ask
 // for goes to txbuf and a wave per answer copies it in.
 //
-// Cost shape: k_txs_values is the call's hashing, k_exp_values<true>'s loop
-// (export_kernels.hip) with another destination: a lane runs (vLen + 9 + 63) /
-// 64 compressions and stores each 64-byte block it has turned into message
+// Cost shape: k_txs_values is the call's hashing, the value_lane (value_store.hpp)
+// of export_kernels.hip's k_exp_values<true> with another destination
+// (TxsValues): a lane runs (vLen + 9 + 63) / 64 compressions and stores each 64-byte block it has turned into message
 // words, lanes take values in length-class order.  Every byte of a Tx is
 // written by exactly one lane, and a dword only by the lane that owns all four
 // of its bytes.
@@ -48,22 +48,7 @@ namespace mh {
 
 namespace {
 
-inline unsigned grid_for(uint64_t threads, unsigned block) {
-    return (unsigned)((threads + block - 1) / block);
-}
-
 constexpr uint64_t kNoSlot = ~0ull;
-
-// the variant that owns item i: item_off[v] <= i < item_off[v + 1]
-__device__ __forceinline__ uint64_t txs_owner(const TxsArrays &x, uint64_t i) {
-    uint64_t lo = 0, hi = x.V;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (x.item_off[mid + 1] <= i) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // the entry record of item i of variant v
 __device__ __forceinline__ const uint8_t *txs_record(const AnsArrays &a, const TxsArrays &x, uint64_t v,
@@ -103,7 +88,7 @@ __global__ __launch_bounds__(256) void k_txs_heads(const AnsArrays a, const TxsA
 __global__ __launch_bounds__(256) void k_txs_plan(const AnsArrays a, const TxsArrays x) {
     const uint64_t it = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (it >= x.I) return;
-    const uint64_t v = txs_owner(x, it);
+    const uint64_t v = owner_of(x.item_off, x.V, it);
     const uint8_t *r = txs_record(a, x, v, it);
     const AnsEntry t = ans_entry(r);
     const uint32_t mode = x.vmode[v];
@@ -254,7 +239,7 @@ __device__ __forceinline__ uint8_t *txs_entry_at(const TxsArrays &x, uint64_t v,
 __global__ __launch_bounds__(256) void k_txs_entries(const AnsArrays a, const TxsArrays x) {
     const uint64_t it = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (it >= x.I || x.ikind[it] == kTxsDrop) return;
-    const uint64_t v = txs_owner(x, it);
+    const uint64_t v = owner_of(x.item_off, x.V, it);
     if (!x.vdst[v]) return;
     const uint8_t *r = txs_record(a, x, v, it);
     const AnsEntry t = ans_entry(r);
@@ -270,60 +255,37 @@ __global__ __launch_bounds__(256) void k_txs_entries(const AnsArrays a, const Tx
     bw.finish();
 }
 
-// One value per lane, in perm order (or input order when perm is null):
-// SHA-256 of vsrc[i][0 .. vlen[i]) against the hVal its entry stores
-// (readValueAt, immustore.go:3235); a difference leaves the entry's index in
-// gbad of its group (the lowest one).  A value whose Tx is written is stored to
-// its place block by block from the message words.
+// value_lane (value_store.hpp) over the items, their owners the variants: a
+// digest that differs leaves the entry's index in gbad of its group (the lowest
+// one); a value whose Tx is written is stored to its place.
+struct TxsValues {
+    static constexpr bool stores = true;
+    const AnsArrays &a;
+    const TxsArrays &x;
+    uint64_t n;
+    const uint8_t *idle;
+    __device__ __forceinline__ bool skip(uint64_t i) const { return x.skip[i]; }
+    __device__ __forceinline__ const uint8_t *src(uint64_t i) const { return x.vsrc[i]; }
+    __device__ __forceinline__ uint64_t len(uint64_t i) const { return x.vlen[i]; }
+    __device__ __forceinline__ uint64_t owner(uint64_t i) const {
+        return owner_of(x.item_off, x.V, i);
+    }
+    __device__ __forceinline__ bool place(uint64_t i, uint64_t v, uint64_t L, uint8_t *&to) const {
+        if (!x.vdst[v]) return false;
+        to = txs_entry_at(x, v, i) + x.isz[i] - L;
+        return true;
+    }
+    __device__ __forceinline__ const uint8_t *record(uint64_t i, uint64_t v) const {
+        return txs_record(a, x, v, i);
+    }
+    __device__ __forceinline__ void differs(uint64_t i, uint64_t v) const {
+        atomicMin(x.gbad + x.vgroup[v], (uint32_t)(i - x.item_off[v]));
+    }
+};
+
 __global__ __launch_bounds__(256) void k_txs_values(const AnsArrays a, const TxsArrays x,
                                                     const uint32_t *__restrict__ perm) {
-    const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool valid = g < x.I;
-    const uint64_t gc = valid ? g : x.I - 1;
-    const uint64_t i = perm ? (uint64_t)perm[gc] : gc;
-    const bool live = valid && !x.skip[i];
-    const uint64_t L = live ? x.vlen[i] : 0;
-    const uint8_t *src = live ? x.vsrc[i] : a.txlog;
-    const uint32_t nb = live ? (uint32_t)((L + 72) >> 6) : 0u;
-    const uint32_t nbmax = wave_max_u32(nb);
-    uint64_t v = 0;
-    ExpDst d{};
-    uint32_t *al = nullptr, sel = 0, carry = 0;
-    bool copy = false;
-    if (live) {
-        v = txs_owner(x, i);
-        if (x.vdst[v]) {
-            copy = true;
-            d = exp_dst(txs_entry_at(x, v, i) + x.isz[i] - L, L);
-            al = reinterpret_cast<uint32_t *>(d.dst - d.g);
-            sel = be_sel(d.g);
-            for (uint64_t m = 0; m < d.head; m++) d.dst[m] = src[m];
-            for (uint64_t m = d.tail; m < L; m++) d.dst[m] = src[m];
-        }
-    }
-    MsgWalk mw;
-    mw.init(src, L);
-    State s;
-    s.init();
-#pragma unroll 1
-    for (uint32_t b = 0; b < nbmax; b++) {
-        const bool on = b < nb;
-        uint32_t w[16];
-        mw.block(b, nb, on, __ballot(on && b + 2 >= nb) == 0, w);
-        if (copy && on) {
-            store_block(al, b, w, carry, sel, d.q0, d.q1);
-            carry = w[15];
-        }
-        if (on) compress(s, w);
-    }
-    if (!live) return;
-    const uint8_t *r = txs_record(a, x, v, i);
-    const uint32_t ml = rd_be16(r), kl = rd_be16(r + 2 + ml);
-    const uint8_t *hv = r + 4 + ml + kl + 12;
-    uint32_t diff = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) diff |= bswap(rd_le32(hv + 4 * j)) ^ s.h[j];
-    if (diff) atomicMin(x.gbad + x.vgroup[v], (uint32_t)(i - x.item_off[v]));
+    value_lane(TxsValues{a, x, x.I, a.txlog}, perm);
 }
 
 // the value for a variant that is not its group's primary: one wave per value
@@ -331,7 +293,7 @@ __global__ __launch_bounds__(256) void k_txs_copy(const AnsArrays a, const TxsAr
     const uint64_t it = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (it >= x.I || x.ikind[it] != kTxsValue || !x.skip[it]) return;  // wave-uniform
-    const uint64_t v = txs_owner(x, it);
+    const uint64_t v = owner_of(x.item_off, x.V, it);
     if (!x.vdst[v]) return;
     const uint8_t *r = txs_record(a, x, v, it);
     const uint32_t ml = rd_be16(r), kl = rd_be16(r + 2 + ml);
@@ -393,52 +355,44 @@ __global__ __launch_bounds__(256) void k_txs_status(const AnsArrays a, const Txs
 
 }  // namespace
 
-#define TXS_LAUNCH(name, kernel, grid, block, ...)                                \
-    do {                                                                          \
-        if (!(grid)) break;                                                       \
-        TimerScope ts(tm, name, st);                                              \
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, __VA_ARGS__);  \
-        if (hipError_t e = hipGetLastError()) return e;                           \
-    } while (0)
-
 hipError_t launch_txs_variants(hipStream_t st, Timer *tm, const AnsArrays &a, const TxsArrays &x) {
-    TXS_LAUNCH("txs_variants", k_txs_variants, grid_for(x.V, 256), 256, a, x);
-    TXS_LAUNCH("txs_heads", k_txs_heads, grid_for(a.n, 256), 256, a, x);
+    MH_LAUNCH("txs_variants", k_txs_variants, grid_for(x.V, 256), 256, a, x);
+    MH_LAUNCH("txs_heads", k_txs_heads, grid_for(a.n, 256), 256, a, x);
     return hipSuccess;
 }
 
 hipError_t launch_txs_plan(hipStream_t st, Timer *tm, const AnsArrays &a, const TxsArrays &x) {
-    TXS_LAUNCH("txs_plan", k_txs_plan, grid_for(x.I, 256), 256, a, x);
-    TXS_LAUNCH("txs_vsize", k_txs_vsize, grid_for(x.V, 4), 256, a, x);
+    MH_LAUNCH("txs_plan", k_txs_plan, grid_for(x.I, 256), 256, a, x);
+    MH_LAUNCH("txs_vsize", k_txs_vsize, grid_for(x.V, 4), 256, a, x);
     return hipSuccess;
 }
 
 hipError_t launch_txs_size(hipStream_t st, Timer *tm, const AnsArrays &a, const TxsArrays &x) {
-    TXS_LAUNCH("txs_size", k_txs_size, grid_for(a.n, 256), 256, a, x);
+    MH_LAUNCH("txs_size", k_txs_size, grid_for(a.n, 256), 256, a, x);
     return hipSuccess;
 }
 
 hipError_t launch_txs_write(hipStream_t st, Timer *tm, const AnsArrays &a, const TxsArrays &x) {
-    TXS_LAUNCH("txs_place", k_txs_place, grid_for(x.V, 256), 256, a, x);
-    TXS_LAUNCH("txs_header", k_txs_header, grid_for(x.V, 256), 256, a, x);
-    TXS_LAUNCH("txs_entries", k_txs_entries, grid_for(x.I, 256), 256, a, x);
+    MH_LAUNCH("txs_place", k_txs_place, grid_for(x.V, 256), 256, a, x);
+    MH_LAUNCH("txs_header", k_txs_header, grid_for(x.V, 256), 256, a, x);
+    MH_LAUNCH("txs_entries", k_txs_entries, grid_for(x.I, 256), 256, a, x);
     return hipSuccess;
 }
 
 hipError_t launch_txs_values(hipStream_t st, Timer *tm, const AnsArrays &a, const TxsArrays &x,
                              const uint32_t *perm) {
-    TXS_LAUNCH("txs_values", k_txs_values, grid_for(x.I, 256), 256, a, x, perm);
-    TXS_LAUNCH("txs_copy", k_txs_copy, grid_for(x.I, 4), 256, a, x);
+    MH_LAUNCH("txs_values", k_txs_values, grid_for(x.I, 256), 256, a, x, perm);
+    MH_LAUNCH("txs_copy", k_txs_copy, grid_for(x.I, 4), 256, a, x);
     return hipSuccess;
 }
 
 hipError_t launch_txs_assemble(hipStream_t st, Timer *tm, const AnsArrays &a, const TxsArrays &x) {
-    TXS_LAUNCH("txs_assemble", k_txs_assemble, (unsigned)a.n, 64, a, x);
+    MH_LAUNCH("txs_assemble", k_txs_assemble, (unsigned)a.n, 64, a, x);
     return hipSuccess;
 }
 
 hipError_t launch_txs_status(hipStream_t st, Timer *tm, const AnsArrays &a, const TxsArrays &x) {
-    TXS_LAUNCH("txs_status", k_txs_status, grid_for(a.n, 256), 256, a, x);
+    MH_LAUNCH("txs_status", k_txs_status, grid_for(a.n, 256), 256, a, x);
     return hipSuccess;
 }
 
