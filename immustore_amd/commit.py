@@ -18,7 +18,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _native as N
-from .merkle import Context, _addr, default_context
+from .merkle import Context, _addr, _call, default_context
 
 
 class EntrySpec:
@@ -45,8 +45,29 @@ def _csr(items):
     return buf, off
 
 
+def precommit_csr(target, version: int, tx_off, keys, key_off, vals, val_off, md=None,
+                  md_off=None, hval_override=None, use_override=None, expect_eh=None,
+                  max_width: int = 0, hvals_out=None, eh_out=None):
+    """mh_precommit_batch on a CommitPipe, or mh_multi_precommit_batch on a
+    multi.MultiDevice: the raw CSR form (numpy arrays, possibly views of pinned
+    memory).  Returns (hvals [E,32], eh [ntx,32], status [ntx] int32)."""
+    tx_off = np.ascontiguousarray(tx_off, np.uint64)
+    ntx = len(tx_off) - 1
+    ne = int(tx_off[-1] - tx_off[0]) if ntx > 0 else 0
+    hv = hvals_out if hvals_out is not None else np.zeros((max(ne, 1), 32), np.uint8)
+    eh = eh_out if eh_out is not None else np.zeros((max(ntx, 1), 32), np.uint8)
+    st = np.zeros(max(ntx, 1), np.int32)
+    fn, h = _call(target, "precommit_batch")
+    N.check(fn(h, version, max_width, ntx, _addr(tx_off), _addr(keys), _addr(key_off), _addr(md),
+               _addr(md_off), _addr(vals), _addr(val_off), _addr(hval_override),
+               _addr(use_override), _addr(expect_eh), _addr(hv), _addr(eh), _addr(st)))
+    return hv[:ne], eh[:ntx], st[:ntx]
+
+
 class CommitPipe:
     """mh_commit_pipe: per-goroutine (not synchronised)."""
+
+    _abi = "mh_"  # merkle._call
 
     def __init__(self, ctx: Optional[Context] = None, chunk_bytes: int = 0):
         self.ctx = ctx or default_context()
@@ -70,16 +91,8 @@ class CommitPipe:
                       max_width: int = 0, hvals_out=None, eh_out=None):
         """Raw CSR form (numpy arrays, possibly views of pinned memory).
         Returns (hvals [E,32], eh [ntx,32], status [ntx] int32)."""
-        ntx = len(tx_off) - 1
-        ne = int(tx_off[-1] - tx_off[0]) if ntx > 0 else 0
-        hv = hvals_out if hvals_out is not None else np.zeros((max(ne, 1), 32), np.uint8)
-        eh = eh_out if eh_out is not None else np.zeros((max(ntx, 1), 32), np.uint8)
-        st = np.zeros(max(ntx, 1), np.int32)
-        N.check(N.load().mh_precommit_batch(
-            self.handle, version, max_width, ntx, _addr(tx_off), _addr(keys), _addr(key_off),
-            _addr(md), _addr(md_off), _addr(vals), _addr(val_off), _addr(hval_override),
-            _addr(use_override), _addr(expect_eh), _addr(hv), _addr(eh), _addr(st)))
-        return hv[:ne], eh[:ntx], st[:ntx]
+        return precommit_csr(self, version, tx_off, keys, key_off, vals, val_off, md, md_off,
+                             hval_override, use_override, expect_eh, max_width, hvals_out, eh_out)
 
     def precommit(self, version: int, txs: Sequence[Sequence[EntrySpec]], expect_eh=None,
                   max_width: int = 0):

@@ -774,16 +774,22 @@ extern "C" int mh_dev_htree_verify_inclusion_batch(mh_ctx *c, uint64_t np, const
     });
 }
 
+bool htree_verify_args_ok(uint64_t n, const uint64_t *leaf, const uint64_t *width,
+                          const uint64_t *term_off, const uint8_t *digests, const uint8_t *roots,
+                          const uint8_t *ok) {
+    return leaf && width && term_off && digests && roots && ok && monotonic(term_off, n);
+}
+
 // host wrapper: stage, run on the context stream, copy back
 extern "C" int mh_htree_verify_inclusion_batch(mh_ctx *c, uint64_t np, const uint64_t *leaf,
                                                const uint64_t *width, const uint64_t *term_off,
                                                const uint8_t *terms, const uint8_t *digests,
                                                const uint8_t *roots, uint8_t *ok) {
     return mh_guard([&]() -> int {
-        if (!c || (np && (!leaf || !width || !term_off || !digests || !roots || !ok)))
-            return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (!c) return MH_ERR_ILLEGAL_ARGUMENTS;
         if (!np) return MH_OK;
-        if (!monotonic(term_off, np)) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (!htree_verify_args_ok(np, leaf, width, term_off, digests, roots, ok))
+            return MH_ERR_ILLEGAL_ARGUMENTS;
         std::lock_guard<std::mutex> lk(c->mu);
         hipSetDevice(c->device);
         const uint64_t nterms = term_off[np] - term_off[0];

@@ -244,6 +244,28 @@ extern "C" int mh_commit_pipe_free(mh_commit_pipe *p) {
     });
 }
 
+bool precommit_args_ok(int version, uint64_t ntx, const uint64_t *tx_off, const uint64_t *key_off,
+                       const uint8_t *md, const uint64_t *md_off, const uint64_t *val_off,
+                       const uint8_t *hval_override, const uint8_t *use_override,
+                       const int32_t *status) {
+    if ((version != 0 && version != 1) || !tx_off || !key_off || !val_off || !status) return false;
+    if ((hval_override == nullptr) != (use_override == nullptr)) return false;
+    if ((md == nullptr) != (md_off == nullptr)) return false;
+    return monotonic(tx_off, ntx);
+}
+
+bool precommit_entries_ok(const uint64_t *tx_off, uint64_t t0, uint64_t t1, const uint8_t *keys,
+                          const uint64_t *key_off, const uint8_t *md, const uint64_t *md_off,
+                          const uint8_t *vals, const uint64_t *val_off) {
+    const uint64_t e0 = tx_off[t0], e1 = tx_off[t1];
+    for (uint64_t e = e0; e < e1; e++)
+        if (key_off[e + 1] < key_off[e] || val_off[e + 1] < val_off[e] ||
+            (md_off && md_off[e + 1] < md_off[e]))
+            return false;
+    return e1 == e0 || !((key_off[e1] > key_off[e0] && !keys) || (val_off[e1] > val_off[e0] && !vals) ||
+                         (md_off && md_off[e1] > md_off[e0] && !md));
+}
+
 extern "C" int mh_precommit_batch(mh_commit_pipe *p, int version, uint64_t max_width,
                                   uint64_t ntx, const uint64_t *tx_off, const uint8_t *keys,
                                   const uint64_t *key_off, const uint8_t *md,
@@ -254,11 +276,9 @@ extern "C" int mh_precommit_batch(mh_commit_pipe *p, int version, uint64_t max_w
     return mh_guard([&]() -> int {
         if (!p || (version != 0 && version != 1)) return MH_ERR_ILLEGAL_ARGUMENTS;
         if (ntx == 0) return MH_OK;
-        if (!tx_off || !key_off || !val_off || !status) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if ((hval_override == nullptr) != (use_override == nullptr)) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if ((md == nullptr) != (md_off == nullptr)) return MH_ERR_ILLEGAL_ARGUMENTS;
-        for (uint64_t t = 0; t < ntx; t++)
-            if (tx_off[t + 1] < tx_off[t]) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (!precommit_args_ok(version, ntx, tx_off, key_off, md, md_off, val_off, hval_override,
+                               use_override, status))
+            return MH_ERR_ILLEGAL_ARGUMENTS;
         // per-tx errors decided on the host (the Go call would return them):
         // htree.ErrMaxWidthExceeded (htree.go:69-71), ErrMetadataUnsupported for
         // KV metadata under a v0 header (tx.go:691-693)
@@ -288,17 +308,7 @@ extern "C" int mh_precommit_batch(mh_commit_pipe *p, int version, uint64_t max_w
                 if (e1 - e0 > kMaxChunkEntries) break;
                 t1++;
             }
-            bool ok = true;
-            for (uint64_t e = tx_off[t]; e < tx_off[t1] && ok; e++) {
-                ok = key_off[e + 1] >= key_off[e] && val_off[e + 1] >= val_off[e] &&
-                     (!md_off || md_off[e + 1] >= md_off[e]);
-            }
-            if (ok && tx_off[t1] > tx_off[t]) {
-                const uint64_t e0 = tx_off[t], e1 = tx_off[t1];
-                ok = !((key_off[e1] > key_off[e0] && !keys) || (val_off[e1] > val_off[e0] && !vals) ||
-                       (md_off && md_off[e1] > md_off[e0] && !md));
-            }
-            if (!ok) {
+            if (!precommit_entries_ok(tx_off, t, t1, keys, key_off, md, md_off, vals, val_off)) {
                 rc = MH_ERR_ILLEGAL_ARGUMENTS;
                 break;
             }

@@ -168,34 +168,55 @@ __global__ __launch_bounds__(256) void k_doc_final(uint64_t n, const mh_tx_heade
 
 }  // namespace
 
+// The pointers, then the extents: every copy of the call reads [first, last)
+// of an array.  That every offset in between is in order
+// (document_offsets_ordered) the single call checks on the host while the
+// copies run, before any kernel reads through them.
+bool document_args_ok(const mh_document_batch &B, const int32_t *status) {
+    const uint64_t n = B.n;
+    if (!status || !B.doc_off || !B.doc_key_off || !B.tx_hdr || !B.ent_off || !B.ekey_off ||
+        !B.ehval || !B.src_hdr || !B.tgt_hdr || !B.incl_off || !B.cons_off || !B.known_tx_id ||
+        !B.known_alh)
+        return false;
+    if (B.doc_off[n] < B.doc_off[0] || B.doc_key_off[n] < B.doc_key_off[0] ||
+        B.ent_off[n] < B.ent_off[0] || B.incl_off[n] < B.incl_off[0] || B.cons_off[n] < B.cons_off[0])
+        return false;
+    const uint64_t e0 = B.ent_off[0], e1 = B.ent_off[n];
+    if (e1 > e0 && (B.ekey_off[e1] < B.ekey_off[e0] || (B.emd_off && B.emd_off[e1] < B.emd_off[e0])))
+        return false;
+    if ((B.doc_off[n] > B.doc_off[0] && !B.doc) ||
+        (B.doc_key_off[n] > B.doc_key_off[0] && !B.doc_key) ||
+        (e1 > e0 && B.ekey_off[e1] > B.ekey_off[e0] && !B.ekeys) ||
+        (B.emd_off && e1 > e0 && B.emd_off[e1] > B.emd_off[e0] && !B.emd))
+        return false;
+    return (B.incl_off[n] == B.incl_off[0] || B.incl_terms) &&
+           (B.cons_off[n] == B.cons_off[0] || B.cons_terms);
+}
+
+// branch-free loops: the single call runs them under its copies
+bool document_offsets_ordered(const mh_document_batch &B) {
+    const uint64_t n = B.n, e0 = B.ent_off[0], e1 = B.ent_off[n];
+    bool bad = false;
+    for (uint64_t d = 0; d < n; d++)
+        bad |= (B.doc_off[d + 1] < B.doc_off[d]) | (B.doc_key_off[d + 1] < B.doc_key_off[d]) |
+               (B.ent_off[d + 1] < B.ent_off[d]) | (B.incl_off[d + 1] < B.incl_off[d]) |
+               (B.cons_off[d + 1] < B.cons_off[d]);
+    const uint64_t *ko = B.ekey_off, *mo = B.emd_off;
+    for (uint64_t e = e0; e < e1; e++) bad |= ko[e + 1] < ko[e];
+    if (mo)
+        for (uint64_t e = e0; e < e1; e++) bad |= mo[e + 1] < mo[e];
+    return !bad;
+}
+
 extern "C" int mh_verify_document_batch(mh_ctx *c, const mh_document_batch *B, int32_t *status,
                                         uint8_t *target_alh_out) {
     return mh_guard([&]() -> int {
         if (!c || !B || (B->n && !status)) return MH_ERR_ILLEGAL_ARGUMENTS;
         const uint64_t n = B->n;
         if (!n) return MH_OK;
-        if (!B->doc_off || !B->doc_key_off || !B->tx_hdr || !B->ent_off || !B->ekey_off ||
-            !B->ehval || !B->src_hdr || !B->tgt_hdr || !B->incl_off || !B->cons_off ||
-            !B->known_tx_id || !B->known_alh)
-            return MH_ERR_ILLEGAL_ARGUMENTS;
-        // the extents first: every copy below reads [first, last) of an
-        // array; that every offset in between is in order is checked on the
-        // host while the copies run, before any kernel reads through them
-        if (B->doc_off[n] < B->doc_off[0] || B->doc_key_off[n] < B->doc_key_off[0] ||
-            B->ent_off[n] < B->ent_off[0] || B->incl_off[n] < B->incl_off[0] ||
-            B->cons_off[n] < B->cons_off[0])
-            return MH_ERR_ILLEGAL_ARGUMENTS;
-        const uint64_t E = B->ent_off[n] - B->ent_off[0];
-        if (E && (B->ekey_off[B->ent_off[n]] < B->ekey_off[B->ent_off[0]] ||
-                  (B->emd_off && B->emd_off[B->ent_off[n]] < B->emd_off[B->ent_off[0]])))
-            return MH_ERR_ILLEGAL_ARGUMENTS;
-        if ((B->doc_off[n] > B->doc_off[0] && !B->doc) ||
-            (B->doc_key_off[n] > B->doc_key_off[0] && !B->doc_key) ||
-            (E && B->ekey_off[B->ent_off[n]] > B->ekey_off[B->ent_off[0]] && !B->ekeys) ||
-            (B->emd_off && E && B->emd_off[B->ent_off[n]] > B->emd_off[B->ent_off[0]] && !B->emd))
-            return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (!document_args_ok(*B, status)) return MH_ERR_ILLEGAL_ARGUMENTS;
         MH_HIP(hipSetDevice(c->device));
-        const uint64_t e0 = B->ent_off[0];
+        const uint64_t e0 = B->ent_off[0], E = B->ent_off[n] - e0;
 
         // One upload of the caller's arrays as they are (offsets unrebased: the
         // device base pointers are shifted instead), then every step on the
@@ -225,7 +246,6 @@ extern "C" int mh_verify_document_batch(mh_ctx *c, const mh_document_batch *B, i
         const uint64_t dk0 = B->doc_key_off[0], dkb = B->doc_key_off[n] - dk0;
         const uint64_t i0 = B->incl_off[0], ni = B->incl_off[n] - i0;
         const uint64_t c0 = B->cons_off[0], nc = B->cons_off[n] - c0;
-        if ((ni && !B->incl_terms) || (nc && !B->cons_terms)) return MH_ERR_ILLEGAL_ARGUMENTS;
         const uint64_t mdl = B->md_blob ? B->md_blob_len : 0;
         const uint64_t hb = n * sizeof(mh_tx_header);
         std::lock_guard<std::mutex> lk(c->mu);
@@ -317,21 +337,10 @@ extern "C" int mh_verify_document_batch(mh_ctx *c, const mh_document_batch *B, i
                     if (u.bytes) MH_HIP(hipMemcpyAsync(base + u.off, u.src, u.bytes, hipMemcpyHostToDevice, st));
             }
         }
-        // every offset in order (host, under the copies; branch-free loops)
-        {
-            bool bad = false;
-            for (uint64_t d = 0; d < n; d++)
-                bad |= (B->doc_off[d + 1] < B->doc_off[d]) | (B->doc_key_off[d + 1] < B->doc_key_off[d]) |
-                       (B->ent_off[d + 1] < B->ent_off[d]) | (B->incl_off[d + 1] < B->incl_off[d]) |
-                       (B->cons_off[d + 1] < B->cons_off[d]);
-            const uint64_t *ko = B->ekey_off, *mo = B->emd_off;
-            for (uint64_t e = e0; e < e0 + E; e++) bad |= ko[e + 1] < ko[e];
-            if (mo)
-                for (uint64_t e = e0; e < e0 + E; e++) bad |= mo[e + 1] < mo[e];
-            if (bad) {
-                MH_HIP(hipStreamSynchronize(st));  // the copies read the caller's arrays
-                return MH_ERR_ILLEGAL_ARGUMENTS;
-            }
+        // every offset in order (host, under the copies)
+        if (!document_offsets_ordered(*B)) {
+            MH_HIP(hipStreamSynchronize(st));  // the copies read the caller's arrays
+            return MH_ERR_ILLEGAL_ARGUMENTS;
         }
         std::vector<uint64_t> leaf_off(n + 1);
         for (uint64_t d = 0; d <= n; d++) leaf_off[d] = B->ent_off[d] - e0;

@@ -49,6 +49,16 @@ int ventry_decode_group(mh_ctx *c, hipStream_t st, Timer *tm, uint64_t nk, const
 
 }  // namespace
 
+// the frame's rules first: its limit on n, before n sizes the read of key_off
+bool verified_get_args_ok(const mh_verified_get_batch &b, const int32_t *status, const uint8_t *ok,
+                          const uint64_t *new_tx, const uint8_t *new_alh) {
+    if (!b.key_off || !b.at_tx || !b.state_tx || !b.state_alh) return false;
+    if (!PbChunkFrame::args_ok(b.n, b.msgs, b.msg_off, status && ok && new_tx && new_alh))
+        return false;
+    if (!monotonic(b.key_off, b.n)) return false;
+    return b.key_off[b.n] == b.key_off[0] || b.keys;
+}
+
 extern "C" int mh_verify_verifiable_entry_pb_batch(mh_ctx *c, const mh_verified_get_batch *b,
                                                    int32_t *status, uint8_t *ok, uint64_t *new_tx,
                                                    uint8_t *new_alh) {
@@ -56,14 +66,11 @@ extern "C" int mh_verify_verifiable_entry_pb_batch(mh_ctx *c, const mh_verified_
         if (!c || !b) return MH_ERR_ILLEGAL_ARGUMENTS;
         const uint64_t n = b->n;
         if (n == 0) return MH_OK;
-        if (!b->key_off || !b->at_tx || !b->state_tx || !b->state_alh)
-            return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (n <= 0x7fffffffull && !monotonic(b->key_off, n)) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (!verified_get_args_ok(*b, status, ok, new_tx, new_alh)) return MH_ERR_ILLEGAL_ARGUMENTS;
         PbChunkFrame F;
-        if (int e = F.open(c, n, b->msgs, b->msg_off, status && ok && new_tx && new_alh)) return e;
+        if (int e = F.open_checked(c, n, b->msgs, b->msg_off)) return e;
         const uint64_t *key_off = b->key_off;
         const uint64_t k0 = key_off[0], kb = key_off[n] - k0;
-        if (kb && !b->keys) return MH_ERR_ILLEGAL_ARGUMENTS;
         hipStream_t st = c->stream;
         Timer *tm = c->tm();
         F.group();

@@ -368,6 +368,37 @@ bool store_resident(const mh_answer_store &s, const mh_export_vlog *vlogs, uint3
 inline mh_answer_store store_prefix(const mh_export_store &s) {
     return {s.txlog, s.txlog_len, s.clog, s.ntx, s.clog_entry_size, s.max_entries, s.max_key_len};
 }
+// What a single-context batch call refuses by its arguments alone (n > 0; no
+// HIP call, no lock, nothing written), stated beside that call.  Its mh_multi_*
+// form runs the same check on the whole batch before any part starts.
+bool htree_verify_args_ok(uint64_t n, const uint64_t *leaf, const uint64_t *width,
+                          const uint64_t *term_off, const uint8_t *digests, const uint8_t *roots,
+                          const uint8_t *ok);  // capi.hip
+bool dual_proof_v2_args_ok(uint64_t n, const mh_tx_header *src_hdr, const mh_tx_header *tgt_hdr,
+                           const uint64_t *incl_off, const uint8_t *incl_terms, const uint64_t *cons_off,
+                           const uint8_t *cons_terms, const uint64_t *src, const uint64_t *tgt,
+                           const uint8_t *src_alh, const uint8_t *tgt_alh,
+                           const int32_t *status);  // capi_tx.hip
+bool verify_values_args_ok(uint64_t n, const uint8_t *vals, const uint64_t *off, const uint8_t *hvals,
+                           const int32_t *status);  // capi_values.hip
+bool verified_get_args_ok(const mh_verified_get_batch &b, const int32_t *status, const uint8_t *ok,
+                          const uint64_t *new_tx, const uint8_t *new_alh);  // capi_entry.hip
+bool verified_tx_args_ok(const mh_verified_tx_batch &b, const int32_t *status, const uint8_t *ok,
+                         const uint64_t *new_tx, const uint8_t *new_alh);  // capi_vtx.hip
+// capi_commit.hip: mh_precommit_batch's own arguments; the entry offsets and
+// byte pointers of transactions [t0, t1), which the single call checks chunk
+// by chunk under the device work of the chunks before
+bool precommit_args_ok(int version, uint64_t ntx, const uint64_t *tx_off, const uint64_t *key_off,
+                       const uint8_t *md, const uint64_t *md_off, const uint64_t *val_off,
+                       const uint8_t *hval_override, const uint8_t *use_override, const int32_t *status);
+bool precommit_entries_ok(const uint64_t *tx_off, uint64_t t0, uint64_t t1, const uint8_t *keys,
+                          const uint64_t *key_off, const uint8_t *md, const uint64_t *md_off,
+                          const uint8_t *vals, const uint64_t *val_off);
+// capi_doc.hip: mh_verify_document_batch's pointers, extents and byte pointers;
+// every offset in order, which the single call checks while its copies run
+bool document_args_ok(const mh_document_batch &B, const int32_t *status);
+bool document_offsets_ordered(const mh_document_batch &B);
+
 // the answers that fit are a prefix of the batch's bytes
 inline uint64_t fit_prefix(const uint64_t *off, uint64_t n, uint64_t out_cap) {
     uint64_t fit = 0;
@@ -589,17 +620,26 @@ struct PbChunkFrame {
     const uint8_t *msgs = nullptr;
     const uint64_t *msg_off = nullptr;
 
-    // n > 0; have_rest: the caller's other pointers are all there
+    // The frame's arguments (n > 0; have_rest: the caller's other pointers are
+    // all there), by the arguments alone: open() starts with it, and the
+    // mh_multi_* forms run it on the whole batch before any part starts.
+    static bool args_ok(uint64_t n, const uint8_t *msgs, const uint64_t *msg_off, bool have_rest) {
+        if (!msg_off || !have_rest) return false;
+        // a header's md_off is 32 bits over 2 n metadata slots
+        if (2 * n * (uint64_t)kMdSlot > 0xffffffffull) return false;
+        if (n > 0x7fffffffull) return false;  // hipcub's int item count
+        if (!monotonic(msg_off, n)) return false;
+        return msg_off[n] == msg_off[0] || msgs;
+    }
     int open(mh_ctx *c, uint64_t n_, const uint8_t *msgs_, const uint64_t *msg_off_,
              bool have_rest) {
-        if (!msg_off_ || !have_rest) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (!args_ok(n_, msgs_, msg_off_, have_rest)) return MH_ERR_ILLEGAL_ARGUMENTS;
+        return open_checked(c, n_, msgs_, msg_off_);
+    }
+    // for a call whose own argument check ran args_ok already
+    int open_checked(mh_ctx *c, uint64_t n_, const uint8_t *msgs_, const uint64_t *msg_off_) {
         n = n_, msgs = msgs_, msg_off = msg_off_;
-        // a header's md_off is 32 bits over 2 n metadata slots
-        if (2 * n * (uint64_t)kMdSlot > 0xffffffffull) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (n > 0x7fffffffull) return MH_ERR_ILLEGAL_ARGUMENTS;  // hipcub's int item count
-        if (!monotonic(msg_off, n)) return MH_ERR_ILLEGAL_ARGUMENTS;
         m0 = msg_off[0], mb = msg_off[n] - m0;
-        if (mb && !msgs) return MH_ERR_ILLEGAL_ARGUMENTS;
         lk = std::unique_lock<std::mutex>(c->mu);
         MH_HIP(hipSetDevice(c->device));
         MH_HIP(c->copy_lane());

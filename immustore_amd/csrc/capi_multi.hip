@@ -923,14 +923,21 @@ extern "C" int mh_multi_ahtree_append_batch(mh_multi *m, uint64_t n0, const uint
 // for a tx log -- and runs the single-context call of part d on device d from
 // its own thread, so every part crosses its own PCIe link; the outputs are the
 // parts' outputs side by side, byte-equal to one single-context call over the
-// whole batch.  K = 1 is that call.
+// whole batch.  K = 1 is that call.  Every call but the tx log's: forward a
+// batch that goes to context 0 whole; run the single call's own argument check
+// (capi_internal.hpp) on the whole batch, so that a defect returns before any
+// part writes; cut; run the single call on each part's slice.
 // ============================================================================
 namespace {
 
-// [lo, hi) of part d of n items over K parts (nearly equal)
-inline void split_part(uint64_t n, int K, int d, uint64_t &lo, uint64_t &hi) {
-    lo = (uint64_t)((unsigned __int128)n * (unsigned)d / (unsigned)K);
-    hi = (uint64_t)((unsigned __int128)n * (unsigned)(d + 1) / (unsigned)K);
+// the batch goes to context 0 whole
+inline bool whole(const mh_multi *m, uint64_t n) { return m->K == 1 || n < (uint64_t)m->K; }
+
+// K + 1 item bounds splitting n items into K parts of nearly equal counts
+std::vector<uint64_t> split_by_index(uint64_t n, int K) {
+    std::vector<uint64_t> t(K + 1);
+    for (int d = 0; d <= K; d++) t[d] = (uint64_t)((unsigned __int128)n * (unsigned)d / (unsigned)K);
+    return t;
 }
 
 // K + 1 item bounds splitting n items into K parts of nearly equal bytes,
@@ -953,6 +960,49 @@ std::vector<uint64_t> split_by_bytes(uint64_t n, int K, B bytes) {
     return t;
 }
 
+// the same for items laid end to end: item i starts at off[i]
+std::vector<uint64_t> split_by_bytes(uint64_t n, int K, const uint64_t *off) {
+    return split_by_bytes(n, K, [off](uint64_t i) { return off[i]; });
+}
+
+// fn(d, lo, hi) for every non-empty part [t[d], t[d + 1]), each from its own
+// thread; m->mu MUST be held
+template <class F>
+int run_parts(mh_multi *m, const std::vector<uint64_t> &t, F &&fn) {
+    return per_device(m->K, [&](int d) -> int {
+        return t[d + 1] == t[d] ? MH_OK : fn(d, t[d], t[d + 1]);
+    });
+}
+
+// the same, taking m->mu
+template <class F>
+int for_parts(mh_multi *m, const std::vector<uint64_t> &t, F &&fn) {
+    std::lock_guard<std::mutex> lk(m->mu);
+    return run_parts(m, t, fn);
+}
+
+// Part [lo, hi) of a struct batch: the per-item arrays advance to its first
+// item; the arrays that offsets index directly (keys, entries, terms, bytes --
+// and key_off / val_off of the tx answers, which the spec numbers index) are
+// shared.  One list per struct.
+mh_verified_get_batch slice(mh_verified_get_batch p, uint64_t lo, uint64_t hi) {
+    p.n = hi - lo;
+    p.msg_off += lo, p.key_off += lo, p.at_tx += lo, p.state_tx += lo, p.state_alh += 32 * lo;
+    return p;
+}
+mh_verified_tx_batch slice(mh_verified_tx_batch p, uint64_t lo, uint64_t hi) {
+    p.n = hi - lo;
+    p.msg_off += lo, p.kind += lo, p.spec_off += lo;
+    p.at_tx += lo, p.state_tx += lo, p.state_alh += 32 * lo;
+    return p;
+}
+mh_document_batch slice(mh_document_batch p, uint64_t lo, uint64_t hi) {
+    p.n = hi - lo;
+    p.doc_off += lo, p.doc_key_off += lo, p.tx_hdr += lo, p.ent_off += lo, p.src_hdr += lo;
+    p.tgt_hdr += lo, p.incl_off += lo, p.cons_off += lo, p.known_tx_id += lo, p.known_alh += 32 * lo;
+    return p;
+}
+
 }  // namespace
 
 // htree.VerifyInclusion over n proofs (htree.go:166-195), split by index.
@@ -962,15 +1012,12 @@ extern "C" int mh_multi_htree_verify_inclusion_batch(mh_multi *m, uint64_t n, co
                                                      const uint8_t *roots, uint8_t *ok) {
     return mh_guard([&]() -> int {
         if (!m) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (m->K == 1 || n < (uint64_t)m->K)
+        if (whole(m, n))
             return mh_htree_verify_inclusion_batch(m->ctx[0], n, leaf, width, term_off, terms,
                                                    digests, roots, ok);
-        if (!leaf || !width || !term_off || !digests || !roots || !ok) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (!monotonic(term_off, n)) return MH_ERR_ILLEGAL_ARGUMENTS;  // before any part writes ok
-        std::lock_guard<std::mutex> lk(m->mu);
-        return per_device(m->K, [&](int d) -> int {
-            uint64_t lo, hi;
-            split_part(n, m->K, d, lo, hi);
+        if (!htree_verify_args_ok(n, leaf, width, term_off, digests, roots, ok))
+            return MH_ERR_ILLEGAL_ARGUMENTS;
+        return for_parts(m, split_by_index(n, m->K), [&](int d, uint64_t lo, uint64_t hi) {
             return mh_htree_verify_inclusion_batch(m->ctx[d], hi - lo, leaf + lo, width + lo,
                                                    term_off + lo, terms, digests + 32 * lo,
                                                    roots + 32 * lo, ok + lo);
@@ -987,18 +1034,14 @@ extern "C" int mh_multi_verify_dual_proof_v2_batch(
     int32_t *status) {
     return mh_guard([&]() -> int {
         if (!m) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (m->K == 1 || n < (uint64_t)m->K)
+        if (whole(m, n))
             return mh_verify_dual_proof_v2_batch(m->ctx[0], n, src_hdr, tgt_hdr, md_blob,
                                                  md_blob_len, incl_off, incl_terms, cons_off,
                                                  cons_terms, src, tgt, src_alh, tgt_alh, status);
-        if (!src_hdr || !tgt_hdr || !incl_off || !cons_off || !src || !tgt || !src_alh ||
-            !tgt_alh || !status)
+        if (!dual_proof_v2_args_ok(n, src_hdr, tgt_hdr, incl_off, incl_terms, cons_off, cons_terms,
+                                   src, tgt, src_alh, tgt_alh, status))
             return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (!monotonic(incl_off, n) || !monotonic(cons_off, n)) return MH_ERR_ILLEGAL_ARGUMENTS;
-        std::lock_guard<std::mutex> lk(m->mu);
-        return per_device(m->K, [&](int d) -> int {
-            uint64_t lo, hi;
-            split_part(n, m->K, d, lo, hi);
+        return for_parts(m, split_by_index(n, m->K), [&](int d, uint64_t lo, uint64_t hi) {
             return mh_verify_dual_proof_v2_batch(m->ctx[d], hi - lo, src_hdr + lo, tgt_hdr + lo,
                                                  md_blob, md_blob_len, incl_off + lo, incl_terms,
                                                  cons_off + lo, cons_terms, src + lo, tgt + lo,
@@ -1056,10 +1099,7 @@ extern "C" int mh_multi_txlog_validate(mh_multi *m, const uint8_t *buf, uint64_t
             part[d] = HopView{&all, t[d], t[d + 1], p, start(t[d])};
             while (p < all.P.size() && all.P[p].rec < t[d + 1]) p++;
         }
-        std::lock_guard<std::mutex> lk(m->mu);
-        const int st = per_device(K, [&](int d) -> int {
-            const uint64_t t0 = t[d], t1 = t[d + 1];
-            if (t1 == t0) return MH_OK;
+        const int st = for_parts(m, t, [&](int d, uint64_t t0, uint64_t t1) -> int {
             const uint64_t b0 = start(t0), b1 = start(t1);
             const int r = txlog_validate_parsed(m->ctx[d], buf + b0, b1 - b0, max_entries,
                                                 max_key_len, part[d],
@@ -1096,18 +1136,14 @@ extern "C" int mh_multi_verify_values_batch(mh_multi *m, uint64_t n, const uint8
                                             uint64_t *ncorrupted) {
     return mh_guard([&]() -> int {
         if (!m) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (m->K == 1 || n < (uint64_t)m->K)
+        if (whole(m, n))
             return mh_verify_values_batch(m->ctx[0], n, vals, off, vlen, hvals, status, ncorrupted);
-        if (!off || !vlen || !hvals || !status) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (!monotonic(off, n)) return MH_ERR_ILLEGAL_ARGUMENTS;
-        const std::vector<uint64_t> t = split_by_bytes(n, m->K, [&](uint64_t i) { return off[i]; });
+        if (!verify_values_args_ok(n, vals, off, hvals, status)) return MH_ERR_ILLEGAL_ARGUMENTS;
         std::vector<uint64_t> bad(m->K, 0);
-        std::lock_guard<std::mutex> lk(m->mu);
-        const int st = per_device(m->K, [&](int d) -> int {
-            const uint64_t lo = t[d], hi = t[d + 1];
-            if (hi == lo) return MH_OK;
-            return mh_verify_values_batch(m->ctx[d], hi - lo, vals, off + lo, vlen + lo,
-                                          hvals + 32 * lo, status + lo, &bad[d]);
+        const int st = for_parts(m, split_by_bytes(n, m->K, off), [&](int d, uint64_t lo, uint64_t hi) {
+            return mh_verify_values_batch(m->ctx[d], hi - lo, vals, off + lo,
+                                          vlen ? vlen + lo : nullptr, hvals + 32 * lo, status + lo,
+                                          &bad[d]);
         });
         if (st) return st;
         if (ncorrupted) {
@@ -1128,17 +1164,12 @@ extern "C" int mh_multi_verify_dual_proof_v2_pb_batch(mh_multi *m, uint64_t n, c
                                                       const uint8_t *tgt_alh, int32_t *status) {
     return mh_guard([&]() -> int {
         if (!m) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (m->K == 1 || n < (uint64_t)m->K)
+        if (whole(m, n))
             return mh_verify_dual_proof_v2_pb_batch(m->ctx[0], n, msgs, msg_off, src, tgt, src_alh,
                                                     tgt_alh, status);
-        if (!msg_off || !src || !tgt || !src_alh || !tgt_alh || !status) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (!monotonic(msg_off, n)) return MH_ERR_ILLEGAL_ARGUMENTS;
-        const std::vector<uint64_t> t =
-            split_by_bytes(n, m->K, [&](uint64_t i) { return msg_off[i]; });
-        std::lock_guard<std::mutex> lk(m->mu);
-        return per_device(m->K, [&](int d) -> int {
-            const uint64_t lo = t[d], hi = t[d + 1];
-            if (hi == lo) return MH_OK;
+        if (!PbChunkFrame::args_ok(n, msgs, msg_off, src && tgt && src_alh && tgt_alh && status))
+            return MH_ERR_ILLEGAL_ARGUMENTS;
+        return for_parts(m, split_by_bytes(n, m->K, msg_off), [&](int d, uint64_t lo, uint64_t hi) {
             return mh_verify_dual_proof_v2_pb_batch(m->ctx[d], hi - lo, msgs, msg_off + lo, src + lo,
                                                     tgt + lo, src_alh + 32 * lo,
                                                     tgt_alh + 32 * lo, status + lo);
@@ -1156,18 +1187,12 @@ extern "C" int mh_multi_verify_dual_proof_pb_batch(mh_multi *m, uint64_t n, cons
                                                    uint8_t *ok) {
     return mh_guard([&]() -> int {
         if (!m) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (m->K == 1 || n < (uint64_t)m->K)
+        if (whole(m, n))
             return mh_verify_dual_proof_pb_batch(m->ctx[0], n, msgs, msg_off, src, tgt, src_alh,
                                                  tgt_alh, status, ok);
-        if (!msg_off || !src || !tgt || !src_alh || !tgt_alh || !status || !ok)
+        if (!PbChunkFrame::args_ok(n, msgs, msg_off, src && tgt && src_alh && tgt_alh && status && ok))
             return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (!monotonic(msg_off, n)) return MH_ERR_ILLEGAL_ARGUMENTS;
-        const std::vector<uint64_t> t =
-            split_by_bytes(n, m->K, [&](uint64_t i) { return msg_off[i]; });
-        std::lock_guard<std::mutex> lk(m->mu);
-        return per_device(m->K, [&](int d) -> int {
-            const uint64_t lo = t[d], hi = t[d + 1];
-            if (hi == lo) return MH_OK;
+        return for_parts(m, split_by_bytes(n, m->K, msg_off), [&](int d, uint64_t lo, uint64_t hi) {
             return mh_verify_dual_proof_pb_batch(m->ctx[d], hi - lo, msgs, msg_off + lo, src + lo,
                                                  tgt + lo, src_alh + 32 * lo, tgt_alh + 32 * lo,
                                                  status + lo, ok + lo);
@@ -1176,35 +1201,19 @@ extern "C" int mh_multi_verify_dual_proof_pb_batch(mh_multi *m, uint64_t n, cons
 }
 
 // Whole VerifiableGet answers (verifiedGet, pkg/client/client.go:1119-1234)
-// over n messages, split into K parts of nearly equal message bytes; every
-// per-answer array and the key offsets keep their indexing, so part d is the
-// same batch seen from answer t[d].
+// over n messages, split into K parts of nearly equal message bytes.
 extern "C" int mh_multi_verify_verifiable_entry_pb_batch(mh_multi *m,
                                                          const mh_verified_get_batch *b,
                                                          int32_t *status, uint8_t *ok,
                                                          uint64_t *new_tx, uint8_t *new_alh) {
     return mh_guard([&]() -> int {
         if (!m) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (!b || m->K == 1 || b->n < (uint64_t)m->K)
+        if (!b || whole(m, b->n))
             return mh_verify_verifiable_entry_pb_batch(m->ctx[0], b, status, ok, new_tx, new_alh);
-        const uint64_t n = b->n;
-        if (!b->msg_off || !b->key_off || !b->at_tx || !b->state_tx || !b->state_alh || !status ||
-            !ok || !new_tx || !new_alh)
-            return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (n > 0x7fffffffull || !monotonic(b->msg_off, n)) return MH_ERR_ILLEGAL_ARGUMENTS;
-        const std::vector<uint64_t> t =
-            split_by_bytes(n, m->K, [&](uint64_t i) { return b->msg_off[i]; });
-        std::lock_guard<std::mutex> lk(m->mu);
-        return per_device(m->K, [&](int d) -> int {
-            const uint64_t lo = t[d], hi = t[d + 1];
-            if (hi == lo) return MH_OK;
-            mh_verified_get_batch part = *b;
-            part.n = hi - lo;
-            part.msg_off += lo;
-            part.key_off += lo;
-            part.at_tx += lo;
-            part.state_tx += lo;
-            part.state_alh += 32 * lo;
+        if (!verified_get_args_ok(*b, status, ok, new_tx, new_alh)) return MH_ERR_ILLEGAL_ARGUMENTS;
+        const std::vector<uint64_t> t = split_by_bytes(b->n, m->K, b->msg_off);
+        return for_parts(m, t, [&](int d, uint64_t lo, uint64_t hi) {
+            const mh_verified_get_batch part = slice(*b, lo, hi);
             return mh_verify_verifiable_entry_pb_batch(m->ctx[d], &part, status + lo, ok + lo,
                                                        new_tx + lo, new_alh + 32 * lo);
         });
@@ -1213,38 +1222,20 @@ extern "C" int mh_multi_verify_verifiable_entry_pb_batch(mh_multi *m,
 
 // Whole VerifiableTx answers (the verified writes and VerifiedTxByID,
 // pkg/client/client.go:1337-1391, 1554-1583) over n messages, split into K
-// parts of nearly equal message bytes; the per-answer arrays advance to the
-// part's first answer, spec_off with them, and key_off / val_off, which the
-// spec numbers index directly, are shared.
+// parts of nearly equal message bytes.
 extern "C" int mh_multi_verify_verifiable_tx_pb_batch(mh_multi *m, const mh_verified_tx_batch *b,
                                                       int32_t *status, uint8_t *ok,
                                                       uint64_t *new_tx, uint8_t *new_alh,
                                                       uint8_t *eh_out) {
     return mh_guard([&]() -> int {
         if (!m) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (!b || m->K == 1 || b->n < (uint64_t)m->K)
+        if (!b || whole(m, b->n))
             return mh_verify_verifiable_tx_pb_batch(m->ctx[0], b, status, ok, new_tx, new_alh,
                                                     eh_out);
-        const uint64_t n = b->n;
-        if (!b->msg_off || !b->kind || !b->spec_off || !b->key_off || !b->val_off || !b->at_tx ||
-            !b->state_tx || !b->state_alh || !status || !ok || !new_tx || !new_alh)
-            return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (2 * n * (uint64_t)MH_MAX_TX_METADATA_LEN > 0xffffffffull || !monotonic(b->msg_off, n))
-            return MH_ERR_ILLEGAL_ARGUMENTS;
-        const std::vector<uint64_t> t =
-            split_by_bytes(n, m->K, [&](uint64_t i) { return b->msg_off[i]; });
-        std::lock_guard<std::mutex> lk(m->mu);
-        return per_device(m->K, [&](int d) -> int {
-            const uint64_t lo = t[d], hi = t[d + 1];
-            if (hi == lo) return MH_OK;
-            mh_verified_tx_batch part = *b;
-            part.n = hi - lo;
-            part.msg_off += lo;
-            part.kind += lo;
-            part.spec_off += lo;
-            part.at_tx += lo;
-            part.state_tx += lo;
-            part.state_alh += 32 * lo;
+        if (!verified_tx_args_ok(*b, status, ok, new_tx, new_alh)) return MH_ERR_ILLEGAL_ARGUMENTS;
+        const std::vector<uint64_t> t = split_by_bytes(b->n, m->K, b->msg_off);
+        return for_parts(m, t, [&](int d, uint64_t lo, uint64_t hi) {
+            const mh_verified_tx_batch part = slice(*b, lo, hi);
             return mh_verify_verifiable_tx_pb_batch(m->ctx[d], &part, status + lo, ok + lo,
                                                     new_tx + lo, new_alh + 32 * lo,
                                                     eh_out ? eh_out + 32 * lo : nullptr);
@@ -1271,20 +1262,19 @@ extern "C" int mh_multi_precommit_batch(mh_multi *m, int version, uint64_t max_w
         auto pipe = [&](int d) -> int {
             return m->pipe[d] ? MH_OK : mh_commit_pipe_new(m->ctx[d], 0, &m->pipe[d]);
         };
-        if (m->K == 1 || ntx < (uint64_t)m->K) {
+        if (whole(m, ntx)) {
             if (int e = pipe(0)) return e;
             return mh_precommit_batch(m->pipe[0], version, max_width, ntx, tx_off, keys, key_off, md,
                                       md_off, vals, val_off, hval_override, use_override, expect_eh,
                                       hvals_out, eh_out, status);
         }
-        if (!tx_off || !val_off || !status) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (!monotonic(tx_off, ntx)) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (!monotonic(val_off + tx_off[0], tx_off[ntx] - tx_off[0])) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (!precommit_args_ok(version, ntx, tx_off, key_off, md, md_off, val_off, hval_override,
+                               use_override, status) ||
+            !precommit_entries_ok(tx_off, 0, ntx, keys, key_off, md, md_off, vals, val_off))
+            return MH_ERR_ILLEGAL_ARGUMENTS;
         const std::vector<uint64_t> t =
             split_by_bytes(ntx, m->K, [&](uint64_t i) { return val_off[tx_off[i]]; });
-        return per_device(m->K, [&](int d) -> int {
-            const uint64_t lo = t[d], hi = t[d + 1];
-            if (hi == lo) return MH_OK;
+        return run_parts(m, t, [&](int d, uint64_t lo, uint64_t hi) -> int {
             if (int e = pipe(d)) return e;
             return mh_precommit_batch(m->pipe[d], version, max_width, hi - lo, tx_off + lo, keys,
                                       key_off, md, md_off, vals, val_off, hval_override, use_override,
@@ -1297,40 +1287,20 @@ extern "C" int mh_multi_precommit_batch(mh_multi *m, int version, uint64_t max_w
 
 // pkg/verification.VerifyDocument's hashing part (verification.go:37-196)
 // for n documents, split into K parts of nearly equal work (entries + document
-// bytes): part d is the same batch with its per-document arrays advanced to
-// its first document; entry, term and byte arrays are indexed through the
-// offsets, which index them directly, so they are shared.
+// bytes).
 extern "C" int mh_multi_verify_document_batch(mh_multi *m, const mh_document_batch *batch,
                                               int32_t *status, uint8_t *target_alh_out) {
     return mh_guard([&]() -> int {
         if (!m || !batch) return MH_ERR_ILLEGAL_ARGUMENTS;
-        const uint64_t n = batch->n;
-        if (m->K == 1 || n < (uint64_t)m->K)
-            return mh_verify_document_batch(m->ctx[0], batch, status, target_alh_out);
         const mh_document_batch &B = *batch;
-        if (!B.doc_off || !B.doc_key_off || !B.tx_hdr || !B.ent_off || !B.src_hdr || !B.tgt_hdr ||
-            !B.incl_off || !B.cons_off || !B.known_tx_id || !B.known_alh || !status)
+        if (whole(m, B.n)) return mh_verify_document_batch(m->ctx[0], batch, status, target_alh_out);
+        if (!document_args_ok(B, status) || !document_offsets_ordered(B))
             return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (!monotonic(B.ent_off, n) || !monotonic(B.doc_off, n)) return MH_ERR_ILLEGAL_ARGUMENTS;
-        const std::vector<uint64_t> t = split_by_bytes(n, m->K, [&](uint64_t i) {
+        const std::vector<uint64_t> t = split_by_bytes(B.n, m->K, [&](uint64_t i) {
             return (B.ent_off[i] - B.ent_off[0]) * 64 + (B.doc_off[i] - B.doc_off[0]);
         });
-        std::lock_guard<std::mutex> lk(m->mu);
-        return per_device(m->K, [&](int d) -> int {
-            const uint64_t lo = t[d], hi = t[d + 1];
-            if (hi == lo) return MH_OK;
-            mh_document_batch P = B;
-            P.n = hi - lo;
-            P.doc_off = B.doc_off + lo;
-            P.doc_key_off = B.doc_key_off + lo;
-            P.tx_hdr = B.tx_hdr + lo;
-            P.ent_off = B.ent_off + lo;
-            P.src_hdr = B.src_hdr + lo;
-            P.tgt_hdr = B.tgt_hdr + lo;
-            P.incl_off = B.incl_off + lo;
-            P.cons_off = B.cons_off + lo;
-            P.known_tx_id = B.known_tx_id + lo;
-            P.known_alh = B.known_alh + 32 * lo;
+        return for_parts(m, t, [&](int d, uint64_t lo, uint64_t hi) {
+            const mh_document_batch P = slice(B, lo, hi);
             return mh_verify_document_batch(m->ctx[d], &P, status + lo,
                                             target_alh_out ? target_alh_out + 32 * lo : nullptr);
         });

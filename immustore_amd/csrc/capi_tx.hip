@@ -266,6 +266,18 @@ int dual_proof_v2_core(hipStream_t st, Timer *tm, uint64_t n, const mh_tx_header
     return MH_OK;
 }
 
+bool dual_proof_v2_args_ok(uint64_t n, const mh_tx_header *src_hdr, const mh_tx_header *tgt_hdr,
+                           const uint64_t *incl_off, const uint8_t *incl_terms,
+                           const uint64_t *cons_off, const uint8_t *cons_terms, const uint64_t *src,
+                           const uint64_t *tgt, const uint8_t *src_alh, const uint8_t *tgt_alh,
+                           const int32_t *status) {
+    if (!src_hdr || !tgt_hdr || !incl_off || !cons_off || !src || !tgt || !src_alh || !tgt_alh ||
+        !status)
+        return false;
+    if (!monotonic(incl_off, n) || !monotonic(cons_off, n)) return false;
+    return (incl_off[n] == incl_off[0] || incl_terms) && (cons_off[n] == cons_off[0] || cons_terms);
+}
+
 // The caller's per-proof arrays are packed whole into one pinned staging area
 // laid out like their device copies and go up in ONE copy; the offsets keep
 // their base and the term pointers are biased.  The statuses come back there.
@@ -277,13 +289,12 @@ extern "C" int mh_verify_dual_proof_v2_batch(mh_ctx *c, uint64_t n, const mh_tx_
                                              const uint64_t *tgt, const uint8_t *src_alh,
                                              const uint8_t *tgt_alh, int32_t *status) {
     return mh_guard([&]() -> int {
-        if (!c || (n && (!sh || !th || !incl_off || !cons_off || !src || !tgt || !src_alh ||
-                         !tgt_alh || !status)))
-            return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (!c) return MH_ERR_ILLEGAL_ARGUMENTS;
         if (!n) return MH_OK;
-        if (!monotonic(incl_off, n) || !monotonic(cons_off, n)) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (!dual_proof_v2_args_ok(n, sh, th, incl_off, incl_terms, cons_off, cons_terms, src, tgt,
+                                   src_alh, tgt_alh, status))
+            return MH_ERR_ILLEGAL_ARGUMENTS;
         const uint64_t ni = incl_off[n] - incl_off[0], nc = cons_off[n] - cons_off[0];
-        if ((ni && !incl_terms) || (nc && !cons_terms)) return MH_ERR_ILLEGAL_ARGUMENTS;
         const uint64_t md_bytes = md_blob ? md_blob_len : 0, hb = n * sizeof(mh_tx_header);
         std::lock_guard<std::mutex> lk(c->mu);
         MH_HIP(hipSetDevice(c->device));

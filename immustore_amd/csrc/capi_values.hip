@@ -30,6 +30,13 @@ namespace {
 constexpr uint64_t kValChunk = 64ull << 20;  // value bytes per pipelined chunk
 }
 
+// vlen may be NULL (lengths not checked)
+bool verify_values_args_ok(uint64_t n, const uint8_t *vals, const uint64_t *off,
+                           const uint8_t *hvals, const int32_t *status) {
+    if (!off || !hvals || !status || !monotonic(off, n)) return false;
+    return off[n] == off[0] || vals;
+}
+
 // Host memory in and out.  The per-entry arrays go up once; the value bytes
 // go up in chunks of ~64 MiB on the context's copy stream, double-buffered,
 // while the compute stream checks the previous chunk (the call is bound by
@@ -39,11 +46,10 @@ extern "C" int mh_verify_values_batch(mh_ctx *c, uint64_t n, const uint8_t *vals
                                       const uint8_t *hvals, int32_t *status,
                                       uint64_t *ncorrupted) {
     return mh_guard([&]() -> int {
-        if (!c || (n && (!off || !hvals || !status))) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (!c || (n && !verify_values_args_ok(n, vals, off, hvals, status)))
+            return MH_ERR_ILLEGAL_ARGUMENTS;
         if (ncorrupted) *ncorrupted = 0;
         if (!n) return MH_OK;
-        if (!monotonic(off, n)) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (off[n] > off[0] && !vals) return MH_ERR_ILLEGAL_ARGUMENTS;
         MH_HIP(hipSetDevice(c->device));
         std::lock_guard<std::mutex> lk(c->mu);
         MH_HIP(c->copy_lane());

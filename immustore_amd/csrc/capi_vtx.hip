@@ -24,6 +24,37 @@
 // records need no scan.
 #include "capi_internal.hpp"
 
+// the frame's rules first: its limits on n, before n sizes any other read
+bool verified_tx_args_ok(const mh_verified_tx_batch &b, const int32_t *status, const uint8_t *ok,
+                         const uint64_t *new_tx, const uint8_t *new_alh) {
+    const uint64_t n = b.n;
+    if (!b.kind || !b.spec_off || !b.key_off || !b.val_off || !b.at_tx || !b.state_tx || !b.state_alh)
+        return false;
+    if (!PbChunkFrame::args_ok(n, b.msgs, b.msg_off, status && ok && new_tx && new_alh)) return false;
+    if (!monotonic(b.spec_off, n)) return false;
+    const uint64_t s0 = b.spec_off[0], T = b.spec_off[n] - s0;
+    for (uint64_t p = 0; p < n; p++) {
+        const uint64_t K = b.spec_off[p + 1] - b.spec_off[p];
+        switch (b.kind[p]) {
+        case MH_VTX_SET:
+        case MH_VTX_REFERENCE:
+        case MH_VTX_ZADD:
+            if (K != 1) return false;
+            break;
+        case MH_VTX_SET_ALL:
+            if (K < 1) return false;
+            break;
+        case MH_VTX_TX_BY_ID:
+            if (K != 0) return false;
+            break;
+        default: return false;
+        }
+    }
+    if (!monotonic(b.key_off + s0, T) || !monotonic(b.val_off + s0, T)) return false;
+    return (b.key_off[s0 + T] == b.key_off[s0] || b.keys) &&
+           (b.val_off[s0 + T] == b.val_off[s0] || b.vals);
+}
+
 extern "C" int mh_verify_verifiable_tx_pb_batch(mh_ctx *c, const mh_verified_tx_batch *b,
                                                 int32_t *status, uint8_t *ok, uint64_t *new_tx,
                                                 uint8_t *new_alh, uint8_t *eh_out) {
@@ -31,38 +62,13 @@ extern "C" int mh_verify_verifiable_tx_pb_batch(mh_ctx *c, const mh_verified_tx_
         if (!c || !b) return MH_ERR_ILLEGAL_ARGUMENTS;
         const uint64_t n = b->n;
         if (n == 0) return MH_OK;
-        if (!b->kind || !b->spec_off || !b->key_off || !b->val_off || !b->at_tx || !b->state_tx ||
-            !b->state_alh)
-            return MH_ERR_ILLEGAL_ARGUMENTS;
-        // the frame's limit (a header's md_off is 32 bits), before n sizes any read
-        if (2 * n * (uint64_t)kMdSlot > 0xffffffffull) return MH_ERR_ILLEGAL_ARGUMENTS;
-        if (!monotonic(b->spec_off, n)) return MH_ERR_ILLEGAL_ARGUMENTS;
+        if (!verified_tx_args_ok(*b, status, ok, new_tx, new_alh)) return MH_ERR_ILLEGAL_ARGUMENTS;
         const uint64_t *spec_off = b->spec_off, *key_off = b->key_off, *val_off = b->val_off;
         const uint64_t s0 = spec_off[0], T = spec_off[n] - s0;
-        for (uint64_t p = 0; p < n; p++) {
-            const uint64_t K = spec_off[p + 1] - spec_off[p];
-            switch (b->kind[p]) {
-            case MH_VTX_SET:
-            case MH_VTX_REFERENCE:
-            case MH_VTX_ZADD:
-                if (K != 1) return MH_ERR_ILLEGAL_ARGUMENTS;
-                break;
-            case MH_VTX_SET_ALL:
-                if (K < 1) return MH_ERR_ILLEGAL_ARGUMENTS;
-                break;
-            case MH_VTX_TX_BY_ID:
-                if (K != 0) return MH_ERR_ILLEGAL_ARGUMENTS;
-                break;
-            default: return MH_ERR_ILLEGAL_ARGUMENTS;
-            }
-        }
-        if (!monotonic(key_off + s0, T) || !monotonic(val_off + s0, T))
-            return MH_ERR_ILLEGAL_ARGUMENTS;
         const uint64_t k0 = key_off[s0], kb = key_off[s0 + T] - k0;
         const uint64_t v0 = val_off[s0], vb = val_off[s0 + T] - v0;
-        if ((kb && !b->keys) || (vb && !b->vals)) return MH_ERR_ILLEGAL_ARGUMENTS;
         PbChunkFrame F;
-        if (int e = F.open(c, n, b->msgs, b->msg_off, status && ok && new_tx && new_alh)) return e;
+        if (int e = F.open_checked(c, n, b->msgs, b->msg_off)) return e;
         hipStream_t st = c->stream;
         Timer *tm = c->tm();
         F.group();

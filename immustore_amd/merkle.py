@@ -50,6 +50,8 @@ def device_count() -> int:
 class Context:
     """One HIP device + stream (mh_ctx)."""
 
+    _abi = "mh_"  # see _call
+
     def __init__(self, device: int = 0, stream: Optional[int] = None):
         self._lib = N.load()
         h = C.c_void_p()
@@ -96,6 +98,15 @@ def default_context() -> Context:
     if _default_ctx is None:
         _default_ctx = Context(0)
     return _default_ctx
+
+
+def _call(ctx, name: str):
+    """(C function, handle) of the batch call mh_<name> on ctx: a Context
+    (None: the default one), or a multi.MultiDevice, whose form of the call is
+    mh_multi_<name> with the same arguments after the handle.  Every wrapper
+    of a call that has both forms marshals once and targets either."""
+    ctx = ctx or default_context()
+    return getattr(N.load(), ctx._abi + name), ctx.handle
 
 
 def levels_len(n: int) -> int:
@@ -255,7 +266,6 @@ def _csr(items):
 def verify_inclusion_batch(proofs: Sequence[InclusionProof], digests, roots,
                            ctx: Optional[Context] = None) -> np.ndarray:
     """htree.VerifyInclusion (htree.go:166-195) for many proofs at once."""
-    ctx = ctx or default_context()
     n = len(proofs)
     if n == 0:
         return np.zeros(0, bool)
@@ -264,14 +274,29 @@ def verify_inclusion_batch(proofs: Sequence[InclusionProof], digests, roots,
     width = np.array([p.width & 0xFFFFFFFFFFFFFFFF for p in proofs], np.uint64)
     off = np.zeros(n + 1, np.uint64)
     off[1:] = np.cumsum([len(p.terms) for p in proofs])
-    terms = _digests([t for p in proofs for t in p.terms] or [b"\0" * 32])
-    d = _digests(digests)
-    r = _digests(roots)
-    ok = np.zeros(n, np.uint8)
-    N.check(N.load().mh_htree_verify_inclusion_batch(
-        ctx.handle, n, _addr(leaf), _addr(width), _addr(off), _addr(terms), _addr(d), _addr(r),
-        _addr(ok)))
-    return ok.astype(bool)
+    terms = _digests([t for p in proofs for t in p.terms])
+    return verify_inclusion_arrays(leaf, width, off, terms, _digests(digests), _digests(roots), ctx)
+
+
+def verify_inclusion_arrays(leaf, width, term_off, terms, digests, roots,
+                            ctx: Optional[Context] = None) -> np.ndarray:
+    """The same from raw arrays as mh_htree_verify_inclusion_batch takes them
+    (leaf / width uint64 Go-int patterns, CSR term_off, terms (T, 32), digests
+    / roots (n, 32)) -> ok[n] bool."""
+    leaf = np.ascontiguousarray(leaf, np.uint64)
+    width = np.ascontiguousarray(width, np.uint64)
+    off = np.ascontiguousarray(term_off, np.uint64)
+    terms = np.ascontiguousarray(terms, np.uint8).reshape(-1, 32)
+    if terms.size == 0:
+        terms = np.zeros((1, 32), np.uint8)
+    d = np.ascontiguousarray(digests, np.uint8)
+    r = np.ascontiguousarray(roots, np.uint8)
+    n = leaf.size
+    ok = np.zeros(max(n, 1), np.uint8)
+    fn, h = _call(ctx, "htree_verify_inclusion_batch")
+    N.check(fn(h, n, _addr(leaf), _addr(width), _addr(off), _addr(terms), _addr(d), _addr(r),
+               _addr(ok)))
+    return ok[:n].astype(bool)
 
 
 def verify_inclusion(proof: Optional[InclusionProof], digest: bytes, root: bytes,
@@ -554,7 +579,6 @@ def verify_values(vals, off, hvals, vlen=None, ctx: Optional[Context] = None):
     batch (mh_verify_values_batch): value i = vals[off[i]:off[i+1]] (the bytes
     read), hvals (n, 32) the stored hVals, vlen (n,) the stored lengths (or
     None) -> (corrupted count, status int32[n]: 0 or MH_ERR_CORRUPTED_DATA)."""
-    ctx = ctx or default_context()
     off = np.ascontiguousarray(off, np.uint64)
     n = len(off) - 1
     v = np.ascontiguousarray(vals, np.uint8)
@@ -562,7 +586,7 @@ def verify_values(vals, off, hvals, vlen=None, ctx: Optional[Context] = None):
     vl = None if vlen is None else np.ascontiguousarray(vlen, np.uint64)
     st = np.zeros(max(n, 1), np.int32)
     bad = C.c_uint64()
-    N.check(N.load().mh_verify_values_batch(ctx.handle, n, _addr(v) if v.size else None,
-                                            _addr(off), _addr(vl), _addr(hv), _addr(st),
-                                            C.byref(bad)))
+    fn, h = _call(ctx, "verify_values_batch")
+    N.check(fn(h, n, _addr(v) if v.size else None, _addr(off), _addr(vl), _addr(hv), _addr(st),
+               C.byref(bad)))
     return bad.value, st[:n]

@@ -13,6 +13,7 @@ from typing import Sequence, Tuple
 import numpy as np
 
 from . import _native as N
+from . import commit, merkle, txlayer
 from .merkle import _addr, levels_len
 
 
@@ -47,6 +48,8 @@ def peaks_of(dlog: np.ndarray, n: int) -> bytes:
 class MultiDevice:
     """mh_multi over the given device ordinals (a device may repeat: more
     shards than devices, roots gathered by device copies instead of RCCL)."""
+
+    _abi = "mh_multi_"  # merkle._call
 
     def __init__(self, devices: Sequence[int]):
         arr = (C.c_int * len(devices))(*devices)
@@ -147,189 +150,64 @@ class MultiDevice:
             _addr(vo), _addr(ov), _addr(use), _addr(hv), _addr(lv), _addr(root)))
         return hv[:n], (lv[:levels_len(n)] if want_levels else None), root.tobytes()
 
-    # ---- the PCIe-bound batch paths split over the devices (mh_multi_*)
+    # ---- the PCIe-bound batch paths split over the devices (mh_multi_*): the
+    # single-context wrappers, which marshal the arguments, given this clique
+    # in place of a context (merkle._call)
     def htree_verify_inclusion_batch(self, leaf, width, term_off, terms, digests, roots):
-        """Raw arrays as mh_htree_verify_inclusion_batch (leaf / width uint64
-        Go-int patterns, CSR term_off, terms (T, 32), digests / roots (n, 32))
-        -> ok[n] bool; proofs split by index over the devices."""
-        leaf = np.ascontiguousarray(leaf, np.uint64)
-        width = np.ascontiguousarray(width, np.uint64)
-        off = np.ascontiguousarray(term_off, np.uint64)
-        terms = np.ascontiguousarray(terms, np.uint8).reshape(-1, 32)
-        if terms.size == 0:
-            terms = np.zeros((1, 32), np.uint8)
-        d = np.ascontiguousarray(digests, np.uint8)
-        r = np.ascontiguousarray(roots, np.uint8)
-        n = leaf.size
-        ok = np.zeros(max(n, 1), np.uint8)
-        N.check(N.load().mh_multi_htree_verify_inclusion_batch(
-            self.handle, n, _addr(leaf), _addr(width), _addr(off), _addr(terms), _addr(d), _addr(r),
-            _addr(ok)))
-        return ok[:n].astype(bool)
+        """merkle.verify_inclusion_arrays, proofs split by index -> ok[n]."""
+        return merkle.verify_inclusion_arrays(leaf, width, term_off, terms, digests, roots, self)
 
     def verify_dual_proof_v2_batch(self, src_hdrs, tgt_hdrs, md_blob, incl, cons, src, tgt,
                                    src_alh, tgt_alh):
-        """txlayer.verify_dual_proof_v2_batch's arguments -> status[n]; split
-        by index over the devices."""
-        from .txlayer import _blob, _d32, _hdrs, _terms_csr
-        sh, th = _hdrs(src_hdrs), _hdrs(tgt_hdrs)
-        n = sh.size
-        if n == 0:
-            return np.zeros(0, np.int32)
-        mb, ml = _blob(md_blob)
-        io, it = _terms_csr(incl)
-        co, ct = _terms_csr(cons)
-        s = np.asarray(src, np.uint64)
-        t = np.asarray(tgt, np.uint64)
-        sa, ta = _d32(src_alh, n), _d32(tgt_alh, n)
-        st = np.zeros(n, np.int32)
-        N.check(N.load().mh_multi_verify_dual_proof_v2_batch(
-            self.handle, n, _addr(sh), _addr(th), _addr(mb), ml, _addr(io), _addr(it), _addr(co),
-            _addr(ct), _addr(s), _addr(t), _addr(sa), _addr(ta), _addr(st)))
-        return st
+        """txlayer.verify_dual_proof_v2_batch, split by index -> status[n]."""
+        return txlayer.verify_dual_proof_v2_batch(src_hdrs, tgt_hdrs, md_blob, incl, cons, src,
+                                                  tgt, src_alh, tgt_alh, self)
 
     def verify_values(self, vals, off, hvals, vlen=None):
-        """merkle.verify_values over the devices (mh_multi_verify_values_batch:
-        parts of nearly equal value bytes) -> (corrupted count, status[n])."""
-        off = np.ascontiguousarray(off, np.uint64)
-        n = len(off) - 1
-        v = np.ascontiguousarray(vals, np.uint8)
-        hv = np.ascontiguousarray(hvals, np.uint8)
-        vl = None if vlen is None else np.ascontiguousarray(vlen, np.uint64)
-        st = np.zeros(max(n, 1), np.int32)
-        bad = C.c_uint64()
-        N.check(N.load().mh_multi_verify_values_batch(
-            self.handle, n, _addr(v) if v.size else None, _addr(off), _addr(vl), _addr(hv),
-            _addr(st), C.byref(bad)))
-        return bad.value, st[:n]
+        """merkle.verify_values, parts of nearly equal value bytes ->
+        (corrupted count, status[n])."""
+        return merkle.verify_values(vals, off, hvals, vlen, self)
 
     def verify_dual_proof_v2_pb_batch(self, msgs, src, tgt, src_alh, tgt_alh):
-        """txlayer.verify_dual_proof_v2_pb_batch over the devices (parts of
-        nearly equal message bytes) -> status[n]."""
-        from .txlayer import _d32
-        n = len(msgs)
-        if n == 0:
-            return np.zeros(0, np.int32)
-        off = np.zeros(n + 1, np.uint64)
-        off[1:] = np.cumsum([len(x) for x in msgs], dtype=np.uint64)
-        buf = np.frombuffer(b"".join(msgs) + b"\0", np.uint8)
-        s_, t_ = np.asarray(src, np.uint64), np.asarray(tgt, np.uint64)
-        sa, ta = _d32(src_alh, n), _d32(tgt_alh, n)
-        st = np.zeros(n, np.int32)
-        N.check(N.load().mh_multi_verify_dual_proof_v2_pb_batch(
-            self.handle, n, _addr(buf), _addr(off), _addr(s_), _addr(t_), _addr(sa), _addr(ta),
-            _addr(st)))
-        return st
+        """txlayer.verify_dual_proof_v2_pb_batch, parts of nearly equal message
+        bytes -> status[n]."""
+        return txlayer.verify_dual_proof_v2_pb_batch(msgs, src, tgt, src_alh, tgt_alh, self)
 
     def verify_dual_proof_pb_batch(self, msgs, src, tgt, src_alh, tgt_alh):
-        """txlayer.verify_dual_proof_pb_batch (DualProof v1) over the devices
-        (parts of nearly equal message bytes) -> (status[n], ok[n])."""
-        from .txlayer import _d32
-        n = len(msgs)
-        if n == 0:
-            return np.zeros(0, np.int32), np.zeros(0, bool)
-        off = np.zeros(n + 1, np.uint64)
-        off[1:] = np.cumsum([len(x) for x in msgs], dtype=np.uint64)
-        buf = np.frombuffer(b"".join(msgs) + b"\0", np.uint8)
-        s_, t_ = np.asarray(src, np.uint64), np.asarray(tgt, np.uint64)
-        sa, ta = _d32(src_alh, n), _d32(tgt_alh, n)
-        st, ok = np.zeros(n, np.int32), np.zeros(n, np.uint8)
-        N.check(N.load().mh_multi_verify_dual_proof_pb_batch(
-            self.handle, n, _addr(buf), _addr(off), _addr(s_), _addr(t_), _addr(sa), _addr(ta),
-            _addr(st), _addr(ok)))
-        return st, ok.astype(bool)
+        """txlayer.verify_dual_proof_pb_batch (DualProof v1), parts of nearly
+        equal message bytes -> (status[n], ok[n])."""
+        return txlayer.verify_dual_proof_pb_batch(msgs, src, tgt, src_alh, tgt_alh, self)
 
     def verify_verifiable_entry_pb_batch(self, msgs, keys, at_tx, state_tx, state_alh):
-        """txlayer.verify_verifiable_entry_pb_batch (whole VerifiableGet answers)
-        over the devices (parts of nearly equal message bytes) ->
+        """txlayer.verify_verifiable_entry_pb_batch (whole VerifiableGet answers),
+        parts of nearly equal message bytes ->
         (status[n], ok[n], new_tx[n], new_alh[n, 32])."""
-        from .txlayer import pack_verified_get_batch
-        n = len(msgs)
-        if n == 0:
-            return (np.zeros(0, np.int32), np.zeros(0, bool), np.zeros(0, np.uint64),
-                    np.zeros((0, 32), np.uint8))
-        b, keep = pack_verified_get_batch(msgs, keys, at_tx, state_tx, state_alh)
-        st, ok = np.zeros(n, np.int32), np.zeros(n, np.uint8)
-        ntx, nalh = np.zeros(n, np.uint64), np.zeros((n, 32), np.uint8)
-        N.check(N.load().mh_multi_verify_verifiable_entry_pb_batch(
-            self.handle, C.byref(b), _addr(st), _addr(ok), _addr(ntx), _addr(nalh)))
-        del keep
-        return st, ok.astype(bool), ntx, nalh
+        return txlayer.verify_verifiable_entry_pb_batch(msgs, keys, at_tx, state_tx, state_alh,
+                                                        self)
 
     def verify_verifiable_tx_pb_batch(self, msgs, kinds, specs, at_tx, state_tx, state_alh):
-        """txlayer.verify_verifiable_tx_pb_batch (whole VerifiableTx answers) over
-        the devices (parts of nearly equal message bytes) ->
+        """txlayer.verify_verifiable_tx_pb_batch (whole VerifiableTx answers),
+        parts of nearly equal message bytes ->
         (status[n], ok[n], new_tx[n], new_alh[n, 32], eh[n, 32])."""
-        from .txlayer import pack_verified_tx_batch
-        n = len(msgs)
-        if n == 0:
-            return (np.zeros(0, np.int32), np.zeros(0, bool), np.zeros(0, np.uint64),
-                    np.zeros((0, 32), np.uint8), np.zeros((0, 32), np.uint8))
-        b, keep = pack_verified_tx_batch(msgs, kinds, specs, at_tx, state_tx, state_alh)
-        st, ok = np.zeros(n, np.int32), np.zeros(n, np.uint8)
-        ntx, nalh = np.zeros(n, np.uint64), np.zeros((n, 32), np.uint8)
-        eh = np.zeros((n, 32), np.uint8)
-        N.check(N.load().mh_multi_verify_verifiable_tx_pb_batch(
-            self.handle, C.byref(b), _addr(st), _addr(ok), _addr(ntx), _addr(nalh), _addr(eh)))
-        del keep
-        return st, ok.astype(bool), ntx, nalh, eh
+        return txlayer.verify_verifiable_tx_pb_batch(msgs, kinds, specs, at_tx, state_tx,
+                                                     state_alh, self)
 
     def verify_document_batch(self, docs):
-        """txlayer.verify_document_batch over the devices
-        (mh_multi_verify_document_batch) -> (status[n], target_alh[n, 32])."""
-        from .txlayer import pack_document_batch
-        n = len(docs)
-        if n == 0:
-            return np.zeros(0, np.int32), np.zeros((0, 32), np.uint8)
-        b, keep = pack_document_batch(docs)
-        st = np.zeros(n, np.int32)
-        alh = np.zeros((n, 32), np.uint8)
-        N.check(N.load().mh_multi_verify_document_batch(self.handle, C.byref(b), _addr(st),
-                                                        _addr(alh)))
-        del keep
-        return st, alh
+        """txlayer.verify_document_batch, parts of nearly equal entries +
+        document bytes -> (status[n], target_alh[n, 32])."""
+        return txlayer.verify_document_batch(docs, self)
 
     def precommit_csr(self, version: int, tx_off, keys, key_off, vals, val_off, md=None,
                       md_off=None, hval_override=None, use_override=None, expect_eh=None,
                       max_width: int = 0):
-        """commit.CommitPipe.precommit_csr over the devices
-        (mh_multi_precommit_batch: whole transactions, parts of nearly equal
-        value bytes, a commit pipe per device) -> (hvals, eh, status)."""
-        tx_off = np.ascontiguousarray(tx_off, np.uint64)
-        ntx = len(tx_off) - 1
-        ne = int(tx_off[-1] - tx_off[0]) if ntx > 0 else 0
-        hv = np.zeros((max(ne, 1), 32), np.uint8)
-        eh = np.zeros((max(ntx, 1), 32), np.uint8)
-        st = np.zeros(max(ntx, 1), np.int32)
-        N.check(N.load().mh_multi_precommit_batch(
-            self.handle, version, max_width, ntx, _addr(tx_off), _addr(keys), _addr(key_off),
-            _addr(md), _addr(md_off), _addr(vals), _addr(val_off), _addr(hval_override),
-            _addr(use_override), _addr(expect_eh), _addr(hv), _addr(eh), _addr(st)))
-        return hv[:ne], eh[:ntx], st[:ntx]
+        """commit.precommit_csr: whole transactions, parts of nearly equal value
+        bytes, a commit pipe per device -> (hvals, eh, status)."""
+        return commit.precommit_csr(self, version, tx_off, keys, key_off, vals, val_off, md, md_off,
+                                    hval_override, use_override, expect_eh, max_width)
 
     def txlog_validate(self, buf, max_entries: int = 1024, max_key_len: int = 1024,
                        max_txs=None, out=None):
-        """txlayer.txlog_validate over the devices (mh_multi_txlog_validate:
-        the log cut at record boundaries, every part over its own link) ->
-        (status, ntx, consumed, hdrs, alh, per_tx)."""
-        from .txlayer import TX_HEADER
-        b = np.frombuffer(bytes(buf), np.uint8) if not isinstance(buf, np.ndarray) else buf
-        cap = max(1, b.size // 122 + 1)
-        if max_txs is not None:
-            cap = max(1, min(cap, max_txs))
-        if out is not None:
-            hd, alh, sts = out
-            cap = max(1, min(cap, len(alh), len(sts), len(hd) if hd is not None else cap))
-        else:
-            hd = np.empty(cap, TX_HEADER)
-            alh = np.empty((cap, 32), np.uint8)
-            sts = np.empty(cap, np.int32)
-        ntx, used = C.c_uint64(0), C.c_uint64(0)
-        rc = N.load().mh_multi_txlog_validate(self.handle, _addr(b) if b.size else None, b.size,
-                                              max_entries, max_key_len, cap, C.byref(ntx),
-                                              C.byref(used), _addr(hd) if hd is not None else None,
-                                              _addr(alh), _addr(sts))
-        if rc < 0:
-            N.check(rc)
-        k = ntx.value
-        return rc, k, used.value, (hd[:k] if hd is not None else None), alh[:k], sts[:k]
+        """txlayer.txlog_validate: the log cut at record boundaries, every part
+        over its own link -> (status, ntx, consumed, hdrs, alh, per_tx)."""
+        return txlayer.txlog_validate(buf, max_entries, max_key_len, max_txs, self, out)
+

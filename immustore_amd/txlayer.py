@@ -19,7 +19,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as N
-from .merkle import Context, _addr, _u8, default_context
+from .merkle import Context, _addr, _call, _u8, default_context
 
 TX_HEADER = np.dtype([("id", "<u8"), ("ts", "<i8"), ("bl_tx_id", "<u8"), ("bl_root", "u1", 32),
                       ("prev_alh", "u1", 32), ("eh", "u1", 32), ("version", "<u4"),
@@ -123,9 +123,9 @@ def verify_dual_proof_v2_batch(src_hdrs, tgt_hdrs, md_blob, incl, cons, src, tgt
     t = np.asarray(tgt, np.uint64)
     sa, ta = _d32(src_alh, n), _d32(tgt_alh, n)
     st = np.zeros(n, np.int32)
-    N.check(N.load().mh_verify_dual_proof_v2_batch(
-        _ctx(ctx).handle, n, _addr(sh), _addr(th), _addr(mb), ml, _addr(io), _addr(it),
-        _addr(co), _addr(ct), _addr(s), _addr(t), _addr(sa), _addr(ta), _addr(st)))
+    fn, h = _call(ctx, "verify_dual_proof_v2_batch")
+    N.check(fn(h, n, _addr(sh), _addr(th), _addr(mb), ml, _addr(io), _addr(it), _addr(co),
+               _addr(ct), _addr(s), _addr(t), _addr(sa), _addr(ta), _addr(st)))
     return st
 
 
@@ -239,8 +239,8 @@ def call_document_batch(b, n, ctx: Optional[Context] = None):
     """mh_verify_document_batch over a batch packed by pack_document_batch."""
     st = np.zeros(n, np.int32)
     alh = np.zeros((n, 32), np.uint8)
-    N.check(N.load().mh_verify_document_batch(_ctx(ctx).handle, C.byref(b), _addr(st),
-                                              _addr(alh)))
+    fn, h = _call(ctx, "verify_document_batch")
+    N.check(fn(h, C.byref(b), _addr(st), _addr(alh)))
     return st, alh
 
 
@@ -367,10 +367,10 @@ def txlog_validate(buf, max_entries: int = DEFAULT_MAX_TX_ENTRIES,
     ntx, used = C.c_uint64(0), C.c_uint64(0)
     lim = cap if max_txs is None else min(cap, max_txs)
     if dev is None:
-        rc = N.load().mh_txlog_validate(_ctx(ctx).handle, _addr(b) if b.size else None, b.size,
-                                        max_entries, max_key_len, lim, C.byref(ntx),
-                                        C.byref(used), _addr(hd) if hd is not None else None,
-                                        _addr(alh), _addr(sts))
+        fn, h = _call(ctx, "txlog_validate")
+        rc = fn(h, _addr(b) if b.size else None, b.size, max_entries, max_key_len, lim,
+                C.byref(ntx), C.byref(used), _addr(hd) if hd is not None else None, _addr(alh),
+                _addr(sts))
     else:
         rc = N.load().mh_txlog_validate_resident(
             _ctx(ctx).handle, _addr(b) if b.size else None, dev, b.size, max_entries, max_key_len,
@@ -588,9 +588,8 @@ def verify_dual_proof_v2_pb_batch(msgs, src, tgt, src_alh, tgt_alh,
     s_, t_ = np.asarray(src, np.uint64), np.asarray(tgt, np.uint64)
     sa, ta = _d32(src_alh, n), _d32(tgt_alh, n)
     st = np.zeros(n, np.int32)
-    N.check(N.load().mh_verify_dual_proof_v2_pb_batch(_ctx(ctx).handle, n, _addr(buf), _addr(off),
-                                                      _addr(s_), _addr(t_), _addr(sa), _addr(ta),
-                                                      _addr(st)))
+    fn, h = _call(ctx, "verify_dual_proof_v2_pb_batch")
+    N.check(fn(h, n, _addr(buf), _addr(off), _addr(s_), _addr(t_), _addr(sa), _addr(ta), _addr(st)))
     return st
 
 
@@ -608,9 +607,9 @@ def verify_dual_proof_pb_batch(msgs, src, tgt, src_alh, tgt_alh, ctx: Optional[C
     s_, t_ = np.asarray(src, np.uint64), np.asarray(tgt, np.uint64)
     sa, ta = _d32(src_alh, n), _d32(tgt_alh, n)
     st, ok = np.zeros(n, np.int32), np.zeros(n, np.uint8)
-    N.check(N.load().mh_verify_dual_proof_pb_batch(_ctx(ctx).handle, n, _addr(buf), _addr(off),
-                                                   _addr(s_), _addr(t_), _addr(sa), _addr(ta),
-                                                   _addr(st), _addr(ok)))
+    fn, h = _call(ctx, "verify_dual_proof_pb_batch")
+    N.check(fn(h, n, _addr(buf), _addr(off), _addr(s_), _addr(t_), _addr(sa), _addr(ta), _addr(st),
+               _addr(ok)))
     return st, ok.astype(bool)
 
 
@@ -672,8 +671,8 @@ def verify_verifiable_entry_pb_batch(msgs, keys, at_tx, state_tx, state_alh,
     b, keep = pack_verified_get_batch(msgs, keys, at_tx, state_tx, state_alh, lead)
     st, ok = np.zeros(n, np.int32), np.zeros(n, np.uint8)
     ntx, nalh = np.zeros(n, np.uint64), np.zeros((n, 32), np.uint8)
-    N.check(N.load().mh_verify_verifiable_entry_pb_batch(_ctx(ctx).handle, C.byref(b), _addr(st),
-                                                         _addr(ok), _addr(ntx), _addr(nalh)))
+    fn, h = _call(ctx, "verify_verifiable_entry_pb_batch")
+    N.check(fn(h, C.byref(b), _addr(st), _addr(ok), _addr(ntx), _addr(nalh)))
     del keep
     return st, ok.astype(bool), ntx, nalh
 
@@ -773,8 +772,7 @@ def verify_verifiable_tx_pb_batch(msgs, kinds, specs, at_tx, state_tx, state_alh
     b, keep = pack_verified_tx_batch(msgs, kinds, specs, at_tx, state_tx, state_alh, lead)
     st, ok = np.zeros(n, np.int32), np.zeros(n, np.uint8)
     ntx, nalh, eh = np.zeros(n, np.uint64), np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8)
-    N.check(N.load().mh_verify_verifiable_tx_pb_batch(_ctx(ctx).handle, C.byref(b), _addr(st),
-                                                      _addr(ok), _addr(ntx), _addr(nalh),
-                                                      _addr(eh)))
+    fn, h = _call(ctx, "verify_verifiable_tx_pb_batch")
+    N.check(fn(h, C.byref(b), _addr(st), _addr(ok), _addr(ntx), _addr(nalh), _addr(eh)))
     del keep
     return st, ok.astype(bool), ntx, nalh, eh

@@ -988,7 +988,11 @@ int mh_dev_ahtree_range_finish(mh_ctx *ctx, uint64_t n0, const uint8_t *peaks, u
  * bytes) for a tx log -- and part d runs the single-context call on device d
  * from its own thread, over its own PCIe link; outputs land side by side,
  * byte-equal to one single-context call over the whole batch (K = 1 IS that
- * call).  Arguments, statuses and outputs as mh_htree_verify_inclusion_batch
+ * call).  The single-context call's argument check runs on the whole batch
+ * before any part starts, so MH_ERR_ILLEGAL_ARGUMENTS comes back with no
+ * output byte written, and the limits a call puts on n (the wire and answer
+ * calls: n <= 2^31 - 1 and 2 n metadata slots within 32 bits) hold for the
+ * whole batch, not per part.  Arguments, statuses and outputs as mh_htree_verify_inclusion_batch
  * (htree.go:166-195), mh_verify_dual_proof_v2_batch (verification.go:303-372)
  * and mh_txlog_validate (tx.go:388-630; the replay of
  * immustore.go:1198-1223 and the indexer's readTx, indexer.go:570: every
